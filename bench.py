@@ -16,6 +16,20 @@ ZeRO-1 AdamW.
 
 ``--model vit`` benchmarks the ViT-MNIST config instead
 (micro 16 × grad_acc 4 = 64 images/replica/step).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time the K steps, print the result line.  ``--full`` adds the secondary
+measurements (the per-phase timing of one warmup step on pipeline
+meshes).  ``--dump-outputs DIR`` writes what the last timed step
+computed (loss, logits without the -inf vocab-padding columns, updated
+parameters; seeded samples of the large ones) as ``DIR/<name>.npy``
+after the timed region, every value finite.  With the option the step
+keeps a reference to its last loss and logits (3.3 GB of bf16 logits for
+GPT-2 124M at micro-batch 32, inside the captured graph's memory pool),
+so such a run's memory layout differs from a plain run's; the timed
+kernels are the same.  Multi-rank runs write ``<name>.rank<r>.npy`` per
+rank.  Weights and data are seeded, so the same arguments give the same
+inputs on every run.
 """
 
 from __future__ import annotations
@@ -72,6 +86,12 @@ def parse_args():
     p.add_argument("--tiny", action="store_true", help="tiny model for CPU smoke runs")
     p.add_argument("--sequence-parallel", action="store_true",
                    help="Megatron-SP over the TP axis (GPT-2)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (per-phase "
+                        "timing of one warmup step on pipeline meshes)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last step's "
+                        "outputs to DIR/<name>.npy (float32)")
     return p.parse_args()
 
 
@@ -202,6 +222,58 @@ def build_vit(args, pg, device, dtype):
     return model, None
 
 
+# --dump-outputs budget: every array is float32; the total stays far
+# below 64 MB (logits 4 MB + <= 64 KB per parameter tensor)
+_DUMP_LOGITS = 1 << 20
+_DUMP_PER_PARAM = 1 << 14
+
+
+def _sample(t, limit, seed, width=None):
+    """``t`` as a flat float32 numpy array; tensors above ``limit``
+    elements are reduced to a fixed (seeded, sorted) sample of indices.
+    ``width`` keeps only the first ``width`` entries of the last dim."""
+    t = t.detach()
+    if width is not None and width < t.shape[-1]:
+        t = t[..., :width]
+    n = t.numel()
+    if n > limit:
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        idx = torch.randint(0, n, (limit,), generator=g).sort().values
+        idx = idx.to(t.device)
+        w = t.shape[-1]
+        # row/column gather: no contiguous copy of a sliced tensor
+        t = t.reshape(-1, w)[idx // w, idx % w]
+    return t.reshape(-1).float().cpu().numpy()
+
+
+def dump_outputs(out_dir, model, last, rank, world_size):
+    """Write what the last timed step produced: its loss and logits
+    (where this rank has them) and the parameters it left behind.
+    The vocab-padding logits columns (-inf by construction, never read by
+    a caller) are left out: ``last["logits_pad"]`` trailing columns."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f".rank{rank}" if world_size > 1 else ""
+    arrays = {}
+    if last.get("loss") is not None:
+        loss = last["loss"]
+        if torch.is_tensor(loss):
+            loss = loss.detach().float().cpu().item()
+        arrays["loss"] = np.asarray([loss], dtype=np.float32)
+    if last.get("logits") is not None:
+        logits = last["logits"]
+        width = logits.shape[-1] - last.get("logits_pad", 0)
+        arrays["logits"] = _sample(logits, _DUMP_LOGITS, 4321, width)
+    params = [_sample(p, _DUMP_PER_PARAM, 5000 + i)
+              for i, p in enumerate(model.parameters())]
+    if params:
+        arrays["params"] = np.concatenate(params)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"),
+                a.astype(np.float32, copy=False))
+
+
 class _ListLoader:
     """PipelineDataLoader-compatible infinite loader over device-resident batches."""
 
@@ -248,6 +320,9 @@ def main():
     pg = init_process_groups("cuda" if use_cuda else "cpu", mesh, ["dp", "tp", "pp"])
     device = pg.device
     rank = pg.rank
+    # seeded weights (the data generators below are seeded too): the same
+    # arguments give the same inputs on every run
+    torch.manual_seed(1234 + rank)
 
     if args.model == "gpt2":
         # pp>1 wants >=4 micro-batches for 1F1B overlap; pp=1 prefers
@@ -297,6 +372,12 @@ def main():
         optimizer = ZeroRedundancyAdamW(model.parameters(), **zero_kw)
 
     criterion = torch.nn.CrossEntropyLoss(ignore_index=-100)
+    # --dump-outputs: the step keeps a reference to its last loss/logits
+    last = {}
+    keep = args.dump_outputs is not None
+    if args.model == "gpt2" and pg.tp_rank == pg.tp_size - 1:
+        # the padding columns sit at the end of the (last shard's) logits
+        last["logits_pad"] = cfg.padded_vocab_size - cfg.vocab_size
 
     if pg.pp_size > 1:
         groups = pg.get_all_groups()
@@ -313,7 +394,9 @@ def main():
         shapes = (micro_b, pipe_shape_seq if task == "clm" else seq, hidden)
 
         def step():
-            ptrainer.train_step(loader, shapes, device, dtype)
+            metrics = ptrainer.train_step(loader, shapes, device, dtype)
+            if keep and isinstance(metrics, dict):
+                last["loss"] = metrics.get("loss")
 
     else:
         is_ddp = isinstance(model, DataParallel)
@@ -329,8 +412,11 @@ def main():
                     logits = model(b["input_ids"])
                     loss = causal_lm_loss(logits, b["labels"], -100)
                 else:
-                    loss = criterion(model(b["images"]), b["labels"])
+                    logits = model(b["images"])
+                    loss = criterion(logits, b["labels"])
                 (loss / grad_acc).backward()
+                if keep:
+                    last["loss"], last["logits"] = loss.detach(), logits.detach()
             if is_ddp:
                 model.finalize_gradients()
             optimizer.step()
@@ -412,7 +498,8 @@ def main():
 
     phase_ms = None
     for wi in range(args.warmup):
-        if wi == args.warmup - 1 and pg.world_size > 1 and pg.pp_size > 1:
+        if (args.full and wi == args.warmup - 1 and pg.world_size > 1
+                and pg.pp_size > 1):
             # overlap evidence: per-phase HIP-event times for ONE warmup
             # step (forward/backward/P2P comm/optimizer) — reported in
             # the JSON, never inside the timed region
@@ -465,6 +552,8 @@ def main():
         print(f"# torch-profiler trace -> {tr}", flush=True)
     if wd:
         wd.stop()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, model, last, rank, pg.world_size)
 
     t = torch.tensor([elapsed], dtype=torch.float64)
     if dist.is_initialized():

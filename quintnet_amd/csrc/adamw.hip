@@ -30,7 +30,7 @@ __global__ void adamw_kernel(
 }
 
 template <typename T>
-__global__ void sumsq_kernel(const T* __restrict__ x, long long n, float* __restrict__ out) {
+__global__ void sumsq_kernel(const T* __restrict__ x, long long n, float* __restrict__ part) {
   __shared__ float scratch[8];
   float acc = 0.f;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -39,7 +39,13 @@ __global__ void sumsq_kernel(const T* __restrict__ x, long long n, float* __rest
     acc += v * v;
   }
   acc = block_reduce_sum<4>(acc, scratch);
-  if (threadIdx.x == 0) atomicAdd(out, acc);
+  // one partial per block, folded by the caller in a fixed order (no
+  // atomics: the clip factor is bit-reproducible run to run)
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+long long sumsq_blocks(long long n) {
+  return min((n + 255) / 256, (long long)2048);
 }
 
 template <typename TP, typename TG>
@@ -55,9 +61,11 @@ void adamw_launch(TP* param, float* master, const TG* grad, float* m, float* v,
 }
 
 template <typename T>
-void sumsq_launch(const T* x, long long n, float* out, hipStream_t stream) {
-  long long blocks = min((n + 255) / 256, (long long)2048);
-  hipLaunchKernelGGL((sumsq_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, stream, x, n, out);
+void sumsq_launch(const T* x, long long n, float* part, hipStream_t stream) {
+  // part: sumsq_blocks(n) floats
+  long long blocks = sumsq_blocks(n);
+  if (blocks <= 0) return;
+  hipLaunchKernelGGL((sumsq_kernel<T>), dim3((unsigned)blocks), dim3(256), 0, stream, x, n, part);
 }
 
 template void adamw_launch<float, float>(float*, float*, const float*, float*, float*, const long long*, long long, float, float, float, float, float, int, hipStream_t);

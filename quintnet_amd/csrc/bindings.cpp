@@ -10,6 +10,7 @@ template <typename T>
 void layernorm_fwd_launch(const T*, const T*, const T*, const T*, T*, T*, float*, float*, int, int, float, hipStream_t);
 template <typename T>
 void layernorm_bwd_launch(const T*, const T*, const T*, const float*, const float*, const T*, T*, float*, float*, int, int, hipStream_t);
+int layernorm_bwd_chunks(int rows);
 template <typename T>
 void softmax_fwd_launch(const T*, T*, long long, int, int, float, int, hipStream_t);
 template <typename T>
@@ -35,11 +36,13 @@ void dropout_bwd_launch(const T*, T*, const unsigned char*, long long, float, hi
 template <typename T>
 void embedding_pair_fwd_launch(const long long*, const T*, const T*, T*, long long, int, int, hipStream_t);
 template <typename T>
-void embedding_pair_bwd_launch(const long long*, const T*, float*, float*, long long, int, int, hipStream_t);
+void embedding_pair_bwd_launch(const long long*, const long long*, const T*, float*, float*, float*, long long, long long, int, int, hipStream_t);
+long long embedding_bwd_chunks(long long rows);
 template <typename TP, typename TG>
 void adamw_launch(TP*, float*, const TG*, float*, float*, const long long*, long long, float, float, float, float, float, int, hipStream_t);
 template <typename T>
 void sumsq_launch(const T*, long long, float*, hipStream_t);
+long long sumsq_blocks(long long n);
 std::vector<at::Tensor> gemm_bias_gelu_aux(at::Tensor x, at::Tensor w,
                                            at::Tensor bias);  // blaslt.cpp
 void gemm_nt_launch(const unsigned short*, const unsigned short*, const unsigned short*,
@@ -156,8 +159,12 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   int64_t H = xc.size(-1);
   int64_t rows = xc.numel() / H;
   auto dx = torch::empty_like(xc);
-  auto dwf = torch::zeros({H}, xc.options().dtype(torch::kFloat32));
-  auto dbf = torch::zeros({H}, xc.options().dtype(torch::kFloat32));
+  // [2 (dw, db), chunks, H] per-chunk partials, folded over chunks below in
+  // a fixed order (bit-reproducible, no atomics)
+  int64_t chunks = layernorm_bwd_chunks((int)rows);
+  auto part = torch::empty({2, chunks, H}, xc.options().dtype(torch::kFloat32));
+  float* dwp = part.data_ptr<float>();
+  float* dbp = dwp + chunks * H;
   torch::Tensor dsc;
   bool has_ds = dsum.has_value() && dsum->defined();
   if (has_ds) dsc = dsum->contiguous();
@@ -165,17 +172,16 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
     layernorm_bwd_launch<unsigned short>(
         bf16p(dyc), bf16p(xc), bf16p(wc), mean.data_ptr<float>(),
         rstd.data_ptr<float>(), has_ds ? bf16p(dsc) : nullptr, bf16p_mut(dx),
-        dwf.data_ptr<float>(), dbf.data_ptr<float>(), (int)rows, (int)H,
-        cur_stream());
+        dwp, dbp, (int)rows, (int)H, cur_stream());
   } else {
     layernorm_bwd_launch<float>(
         dyc.data_ptr<float>(), xc.data_ptr<float>(), wc.data_ptr<float>(),
         mean.data_ptr<float>(), rstd.data_ptr<float>(),
         has_ds ? dsc.data_ptr<float>() : nullptr, dx.data_ptr<float>(),
-        dwf.data_ptr<float>(), dbf.data_ptr<float>(), (int)rows, (int)H,
-        cur_stream());
+        dwp, dbp, (int)rows, (int)H, cur_stream());
   }
-  return {dx, dwf.to(w.dtype()), dbf.to(w.dtype())};
+  auto dwdb = part.sum(1).to(w.dtype());  // [2, H]
+  return {dx, dwdb[0], dwdb[1]};
 }
 
 // ---------------------------------------------------------------------------
@@ -226,16 +232,18 @@ std::vector<torch::Tensor> cross_entropy_fwd(torch::Tensor logits,
   int64_t V = lc.size(-1);
   long long rows = lc.numel() / V;
   auto lse = torch::empty({(int64_t)rows}, lc.options().dtype(torch::kFloat32));
-  auto loss_sum = torch::zeros({}, lc.options().dtype(torch::kFloat32));
+  // per-row losses folded in a fixed order: bit-reproducible run to run
+  auto row_loss = torch::empty({(int64_t)rows}, lc.options().dtype(torch::kFloat32));
   if (lc.dtype() == torch::kBFloat16) {
     ce_fwd_launch<unsigned short>(bf16p(lc), (const long long*)tc.data_ptr<int64_t>(),
-                                  lse.data_ptr<float>(), loss_sum.data_ptr<float>(),
+                                  lse.data_ptr<float>(), row_loss.data_ptr<float>(),
                                   rows, (int)V, ignore_index, cur_stream());
   } else {
     ce_fwd_launch<float>(lc.data_ptr<float>(), (const long long*)tc.data_ptr<int64_t>(),
-                         lse.data_ptr<float>(), loss_sum.data_ptr<float>(), rows,
+                         lse.data_ptr<float>(), row_loss.data_ptr<float>(), rows,
                          (int)V, ignore_index, cur_stream());
   }
+  auto loss_sum = row_loss.sum();
   auto n_valid = (tc != ignore_index).sum();
   return {loss_sum, n_valid, lse};
 }
@@ -304,16 +312,30 @@ std::vector<torch::Tensor> embedding_pair_bwd(torch::Tensor ids, torch::Tensor d
   int64_t H = dc.size(-1);
   auto dwte = torch::zeros({vocab, H}, dc.options().dtype(torch::kFloat32));
   auto dwpe = torch::zeros({n_pos, H}, dc.options().dtype(torch::kFloat32));
+  TORCH_CHECK(n_pos >= Tlen, "sequence longer than the position table");
+  TORCH_CHECK(dc.numel() == rows * H, "dout does not match ids");
+  // stable sort: equal tokens keep ascending row order, so each token's
+  // rows are summed in one fixed order (atomic-free, bit-reproducible)
+  auto sorted = ic.reshape({-1}).sort(/*stable=*/true, /*dim=*/0, /*descending=*/false);
+  auto sid = std::get<0>(sorted).contiguous();
+  auto perm = std::get<1>(sorted).contiguous();
+  // per-chunk partials of token runs that cross chunk borders
+  auto part = torch::empty({(int64_t)embedding_bwd_chunks(rows), 2, H},
+                           dc.options().dtype(torch::kFloat32));
   if (dc.dtype() == torch::kBFloat16)
     embedding_pair_bwd_launch<unsigned short>(
-        (const long long*)ic.data_ptr<int64_t>(), bf16p(dc),
-        dwte.data_ptr<float>(), dwpe.data_ptr<float>(), rows, (int)Tlen, (int)H,
-        cur_stream());
+        (const long long*)sid.data_ptr<int64_t>(),
+        (const long long*)perm.data_ptr<int64_t>(), bf16p(dc),
+        dwte.data_ptr<float>(), dwpe.data_ptr<float>(), part.data_ptr<float>(),
+        rows, (long long)vocab,
+        (int)Tlen, (int)H, cur_stream());
   else
     embedding_pair_bwd_launch<float>(
-        (const long long*)ic.data_ptr<int64_t>(), dc.data_ptr<float>(),
-        dwte.data_ptr<float>(), dwpe.data_ptr<float>(), rows, (int)Tlen, (int)H,
-        cur_stream());
+        (const long long*)sid.data_ptr<int64_t>(),
+        (const long long*)perm.data_ptr<int64_t>(), dc.data_ptr<float>(),
+        dwte.data_ptr<float>(), dwpe.data_ptr<float>(), part.data_ptr<float>(),
+        rows, (long long)vocab,
+        (int)Tlen, (int)H, cur_stream());
   return {dwte.to(dout.dtype()), dwpe.to(dout.dtype())};
 }
 
@@ -432,16 +454,23 @@ void adamw_step(torch::Tensor param, torch::Tensor master, torch::Tensor grad,
 
 torch::Tensor multi_tensor_sumsq(std::vector<torch::Tensor> tensors) {
   TORCH_CHECK(!tensors.empty(), "empty tensor list");
-  auto out = torch::zeros({}, tensors[0].options().dtype(torch::kFloat32));
+  // every block writes one partial; the partials are folded in a fixed
+  // order afterwards (bit-reproducible, no atomics)
+  int64_t total = 0;
+  for (auto& t : tensors) total += sumsq_blocks(t.numel());
+  auto part = torch::empty({total}, tensors[0].options().dtype(torch::kFloat32));
   auto st = cur_stream();
+  int64_t off = 0;
   for (auto& t : tensors) {
     auto tc = t.contiguous();
+    float* pp = part.data_ptr<float>() + off;
     if (tc.dtype() == torch::kBFloat16)
-      sumsq_launch<unsigned short>(bf16p(tc), tc.numel(), out.data_ptr<float>(), st);
+      sumsq_launch<unsigned short>(bf16p(tc), tc.numel(), pp, st);
     else
-      sumsq_launch<float>(tc.data_ptr<float>(), tc.numel(), out.data_ptr<float>(), st);
+      sumsq_launch<float>(tc.data_ptr<float>(), tc.numel(), pp, st);
+    off += sumsq_blocks(tc.numel());
   }
-  return out;
+  return part.sum();
 }
 
 

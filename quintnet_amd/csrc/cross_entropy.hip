@@ -17,7 +17,7 @@ __device__ __forceinline__ void online_combine(float& m, float& s, float m2, flo
 template <typename T>
 __global__ void ce_fwd_kernel(
     const T* __restrict__ logits, const long long* __restrict__ target,
-    float* __restrict__ lse_out, float* __restrict__ loss_sum,
+    float* __restrict__ lse_out, float* __restrict__ row_loss,
     long long rows, int V, long long ignore_index) {
   __shared__ float sm[8], ss[8];
   const int lane = threadIdx.x & (QN_WAVE - 1);
@@ -72,9 +72,10 @@ __global__ void ce_fwd_kernel(
       for (int i = 1; i < nwaves; ++i) online_combine(M, S, sm[i], ss[i]);
       float lse = M + __logf(S);
       lse_out[row] = lse;
+      // per-row loss (0 for ignored rows); the caller folds the rows in a
+      // fixed order, so the loss is bit-reproducible (no atomics)
       const long long tgt = target[row];
-      if (tgt != ignore_index)
-        atomicAdd(loss_sum, lse - ld_as_f32(lr + (int)tgt));
+      row_loss[row] = (tgt != ignore_index) ? lse - ld_as_f32(lr + (int)tgt) : 0.f;
     }
     __syncthreads();
   }
@@ -148,11 +149,11 @@ __global__ void ce_bwd_kernel(
 
 template <typename T>
 void ce_fwd_launch(const T* logits, const long long* target, float* lse,
-                   float* loss_sum, long long rows, int V, long long ignore_index,
+                   float* row_loss, long long rows, int V, long long ignore_index,
                    hipStream_t stream) {
   int grid = (int)min((long long)2048, rows);
   hipLaunchKernelGGL((ce_fwd_kernel<T>), dim3(grid), dim3(256), 0, stream,
-                     logits, target, lse, loss_sum, rows, V, ignore_index);
+                     logits, target, lse, row_loss, rows, V, ignore_index);
 }
 
 template <typename T>

@@ -5,8 +5,9 @@
 //
 // Backward is two kernels: dx (wave-per-row, no atomics) and a separate
 // dw/db column reduction (block-per-column-tile × row-chunks, one
-// atomicAdd per column per chunk) — the v1 per-element atomic version
-// was 20% of the whole GPT-2 step (rocprof, profiles/r01).
+// partial per column per chunk, folded in a fixed order afterwards) —
+// the v1 per-element atomic version was 20% of the whole GPT-2 step
+// (rocprof, profiles/r01).
 #include "common.h"
 
 // ---------------------------------------------------------------------------
@@ -199,8 +200,8 @@ __global__ void layernorm_bwd_dx_kernel(
 
 // ---------------------------------------------------------------------------
 // backward dw/db: column reduction.  grid = (ceil(H/256), ROW_CHUNKS);
-// each thread owns one column within its row chunk, one atomicAdd per
-// column per chunk.
+// each thread owns one column within its row chunk and writes one partial
+// per column per chunk.
 // ---------------------------------------------------------------------------
 template <typename T>
 __global__ void layernorm_bwd_dwdb_kernel(
@@ -218,9 +219,13 @@ __global__ void layernorm_bwd_dwdb_kernel(
     aw += dyv * xhat;
     ab += dyv;
   }
-  atomicAdd(dw + col, aw);
-  atomicAdd(db + col, ab);
+  // dw/db are [nchunks, H] partials, folded over chunks by the caller in a
+  // fixed order (no atomics: bit-reproducible run to run)
+  dw[(long long)r0 * H + col] = aw;
+  db[(long long)r0 * H + col] = ab;
 }
+
+int layernorm_bwd_chunks(int rows) { return min(max(rows / 64, 1), 256); }
 
 // ---- launchers -------------------------------------------------------------
 template <typename T>
@@ -242,7 +247,8 @@ void layernorm_bwd_launch(const T* dy, const T* x, const T* w, const float* mean
   hipLaunchKernelGGL((layernorm_bwd_dx_kernel<T, WPB>), grid, dim3(WPB * QN_WAVE),
                      0, stream, dy, x, w, mean, rstd, dsum, dx, rows, H);
   int colblocks = (H + 255) / 256;
-  int chunks = min(max(rows / 64, 1), 256);
+  // dw, db: [layernorm_bwd_chunks(rows), H] partials each
+  int chunks = layernorm_bwd_chunks(rows);
   hipLaunchKernelGGL((layernorm_bwd_dwdb_kernel<T>), dim3(colblocks, chunks),
                      dim3(256), 0, stream, dy, x, mean, rstd, dw, db, rows, H);
 }

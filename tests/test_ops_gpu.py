@@ -317,6 +317,66 @@ def test_embedding_pair_fused():
     assert (wpe.grad.float() - wpef.grad).abs().max() / max(float(wpef.grad.abs().max()), 1.0) < 3e-2
 
 
+@pytest.mark.parametrize("dt", [torch.bfloat16, torch.float32])
+def test_embedding_bwd_heavy_duplicates(dt):
+    """Atomic-free scatter-add: token runs inside one 16-position chunk,
+    runs of ~40 that cross chunk borders and one padding-like token that
+    fills about half the rows (a run over ~30 chunks); H=200 is no
+    multiple of the 128-column tile; position table longer than the
+    sequence; a vocab row that never occurs.  fp32 sums of <= ~600
+    addends of |x| ~ 1: error << 1e-3; the bf16 result adds only its final
+    rounding, at most 2^-8 relative."""
+    torch.manual_seed(13)
+    V, P, B, T, H = 40, 160, 8, 125, 200
+    ids = torch.randint(0, V - 1, (B, T), device=DEV)  # token V-1 unused
+    ids[torch.rand(B, T, device=DEV) < 0.5] = 3
+    ids[0, :12] = torch.arange(20, 32, device=DEV)[:12]
+    dout = torch.randn(B, T, H, device=DEV, dtype=dt)
+    dwte, dwpe = _ext().embedding_pair_bwd(ids, dout, V, P)
+    ref_te = torch.zeros(V, H, device=DEV, dtype=torch.float64).index_add_(
+        0, ids.reshape(-1), dout.double().reshape(-1, H)).float()
+    ref_pe = torch.zeros(P, H, device=DEV)
+    ref_pe[:T] = dout.double().sum(0).float()
+    rel = 2.0 ** -8 if dt == torch.bfloat16 else 0.0
+    assert dwte.shape == (V, H) and dwpe.shape == (P, H)
+    assert bool(((dwte.float() - ref_te).abs() <= rel * ref_te.abs() + 1e-3).all())
+    assert bool(((dwpe.float() - ref_pe).abs() <= rel * ref_pe.abs() + 1e-3).all())
+    assert float(dwte[V - 1].abs().max()) == 0.0
+    assert float(dwpe[T:].abs().max()) == 0.0
+
+
+def test_reductions_bit_reproducible():
+    """The reductions that feed the weights and the loss (embedding
+    scatter-add, LayerNorm dw/db, grad-norm sum of squares, CE loss sum)
+    add in a fixed order: the same call twice gives the same bits."""
+    torch.manual_seed(14)
+    e = _ext()
+    ids = torch.randint(0, 16, (8, 128), device=DEV)
+    dout = torch.randn(8, 128, 768, device=DEV, dtype=torch.bfloat16)
+    a, b = e.embedding_pair_bwd(ids, dout, 16, 128), e.embedding_pair_bwd(ids, dout, 16, 128)
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+
+    x = torch.randn(4096, 768, device=DEV, dtype=torch.bfloat16)
+    w = torch.randn(768, device=DEV, dtype=torch.bfloat16)
+    dy = torch.randn_like(x)
+    mean = x.float().mean(-1)
+    rstd = (x.float().var(-1, unbiased=False) + 1e-5).rsqrt()
+    a, b = e.layernorm_bwd(dy, x, w, mean, rstd, None), e.layernorm_bwd(dy, x, w, mean, rstd, None)
+    assert all(torch.equal(p, q) for p, q in zip(a, b))
+
+    # 600k elements: past the 2048-block cap of the sum-of-squares grid
+    xs = [torch.randn(600_000, device=DEV), torch.randn(1000, device=DEV, dtype=torch.bfloat16)]
+    assert torch.equal(e.multi_tensor_sumsq(xs), e.multi_tensor_sumsq(xs))
+    ref = sum(float(t.double().pow(2).sum()) for t in xs)
+    assert abs(float(e.multi_tensor_sumsq(xs)) - ref) / ref < 1e-5
+
+    logits = torch.randn(3000, 1000, device=DEV, dtype=torch.bfloat16)
+    tgt = torch.randint(0, 1000, (3000,), device=DEV)
+    tgt[::7] = -100
+    a, b = e.cross_entropy_fwd(logits, tgt, -100), e.cross_entropy_fwd(logits, tgt, -100)
+    assert torch.equal(a[0], b[0])
+
+
 @pytest.mark.gpu
 def test_flash_attention_q_offset_vs_reference():
     """Rectangular flash attention with a shifted causal diagonal (the CP
