@@ -11,6 +11,11 @@ void layernorm_fwd_launch(const T*, const T*, const T*, const T*, T*, T*, float*
 template <typename T>
 void layernorm_bwd_launch(const T*, const T*, const T*, const float*, const float*, const T*, T*, float*, float*, int, int, hipStream_t);
 int layernorm_bwd_chunks(int rows);
+bool layernorm_bwd_fused_shape_ok(int H);
+void layernorm_bwd_fused_launch(const unsigned short*, const unsigned short*,
+                                const unsigned short*, const float*, const float*,
+                                const unsigned short*, unsigned short*, float*,
+                                float*, int, int, hipStream_t);
 template <typename T>
 void softmax_fwd_launch(const T*, T*, long long, int, int, float, int, hipStream_t);
 template <typename T>
@@ -150,6 +155,11 @@ std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
   return {y, mean, rstd};
 }
 
+bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// The fast shape (bf16, H % 8 == 0, 512 <= H <= 1024) is one pass over dy and
+// x that writes dx and the dw/db chunk partials; every other shape keeps the
+// dx + dwdb kernel pair.  Both write the same partials, folded below.
 std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
                                          torch::Tensor w, torch::Tensor mean,
                                          torch::Tensor rstd,
@@ -158,17 +168,31 @@ std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
   auto dyc = dy.contiguous(); auto xc = x.contiguous(); auto wc = w.contiguous();
   int64_t H = xc.size(-1);
   int64_t rows = xc.numel() / H;
+  TORCH_CHECK(dyc.numel() == xc.numel() && wc.numel() == H &&
+                  mean.numel() == rows && rstd.numel() == rows,
+              "layernorm_bwd: shape mismatch");
   auto dx = torch::empty_like(xc);
+  torch::Tensor dsc;
+  bool has_ds = dsum.has_value() && dsum->defined();
+  if (has_ds) {
+    dsc = dsum->contiguous();
+    TORCH_CHECK(dsc.numel() == xc.numel(), "layernorm_bwd: dsum shape mismatch");
+  }
   // [2 (dw, db), chunks, H] per-chunk partials, folded over chunks below in
   // a fixed order (bit-reproducible, no atomics)
   int64_t chunks = layernorm_bwd_chunks((int)rows);
   auto part = torch::empty({2, chunks, H}, xc.options().dtype(torch::kFloat32));
   float* dwp = part.data_ptr<float>();
   float* dbp = dwp + chunks * H;
-  torch::Tensor dsc;
-  bool has_ds = dsum.has_value() && dsum->defined();
-  if (has_ds) dsc = dsum->contiguous();
-  if (xc.dtype() == torch::kBFloat16) {
+  if (xc.dtype() == torch::kBFloat16 && wc.dtype() == torch::kBFloat16 &&
+      layernorm_bwd_fused_shape_ok((int)H) && aligned16(xc.data_ptr()) &&
+      aligned16(dyc.data_ptr()) && aligned16(wc.data_ptr()) &&
+      aligned16(dx.data_ptr()) && (!has_ds || aligned16(dsc.data_ptr()))) {
+    layernorm_bwd_fused_launch(
+        bf16p(dyc), bf16p(xc), bf16p(wc), mean.data_ptr<float>(),
+        rstd.data_ptr<float>(), has_ds ? bf16p(dsc) : nullptr, bf16p_mut(dx),
+        dwp, dbp, (int)rows, (int)H, cur_stream());
+  } else if (xc.dtype() == torch::kBFloat16) {
     layernorm_bwd_launch<unsigned short>(
         bf16p(dyc), bf16p(xc), bf16p(wc), mean.data_ptr<float>(),
         rstd.data_ptr<float>(), has_ds ? bf16p(dsc) : nullptr, bf16p_mut(dx),
@@ -549,6 +573,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("act") = 0, py::arg("mode") = 0);
   m.def("layernorm_fwd", &layernorm_fwd);
   m.def("layernorm_bwd", &layernorm_bwd);
+  m.def("layernorm_bwd_chunks", [](int64_t rows) {
+    return (int64_t)layernorm_bwd_chunks((int)rows);
+  }, "row chunks (= blocks of the one-pass kernel) LayerNorm backward uses");
   m.def("softmax_fwd", &softmax_fwd);
   m.def("softmax_bwd", &softmax_bwd);
   m.def("cross_entropy_fwd", &cross_entropy_fwd);

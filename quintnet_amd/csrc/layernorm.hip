@@ -7,7 +7,9 @@
 // dw/db column reduction (block-per-column-tile × row-chunks, one
 // partial per column per chunk, folded in a fixed order afterwards) —
 // the v1 per-element atomic version was 20% of the whole GPT-2 step
-// (rocprof, profiles/r01).
+// (rocprof, profiles/r01).  For bf16 with 512 <= H <= 1024 one kernel does
+// both in a single read of dy and x, with the pair's bits
+// (layernorm_bwd_fused_kernel below).
 #include "common.h"
 
 // ---------------------------------------------------------------------------
@@ -226,6 +228,156 @@ __global__ void layernorm_bwd_dwdb_kernel(
 }
 
 int layernorm_bwd_chunks(int rows) { return min(max(rows / 64, 1), 256); }
+
+// ---------------------------------------------------------------------------
+// one-pass backward for the fast shape (bf16, H % 8 == 0, 512 <= H <= 1024):
+// dx and the dw/db chunk partials from ONE read of dy and x, with the bits of
+// the dx + dwdb kernel pair.  Block c owns the dwdb kernel's row chunk c (rows
+// c, c + chunks, c + 2*chunks, ...).  Its waves take LNF_WPB of those rows at
+// a time: each wave computes dx of its row exactly as layernorm_bwd_dx_kernel
+// does and leaves xhat and dy of the row in LDS; then thread t adds the
+// staged rows into its column-t accumulators in row order, which is the
+// sequence of operations layernorm_bwd_dwdb_kernel runs for that column.
+// ---------------------------------------------------------------------------
+constexpr int LNF_WPB = 16;     // waves per block = rows staged per round
+constexpr int LNF_MAXH = 1024;  // 16 columns per lane, one column per thread
+
+__global__ void __launch_bounds__(LNF_WPB * QN_WAVE)
+layernorm_bwd_fused_kernel(
+    const unsigned short* __restrict__ dy, const unsigned short* __restrict__ x,
+    const unsigned short* __restrict__ w, const float* __restrict__ mean_in,
+    const float* __restrict__ rstd_in, const unsigned short* __restrict__ dsum,
+    unsigned short* __restrict__ dx, float* __restrict__ dw,
+    float* __restrict__ db, int rows, int H) {
+  // Results must keep the bits of the two kernels this replaces, so no
+  // contraction is left to the optimizer: an fma is written out exactly
+  // where their compiled code has one (the dwdb kernel has none).
+#pragma clang fp contract(off)
+  __shared__ float s_xhat[LNF_WPB][LNF_MAXH];
+  __shared__ __attribute__((aligned(16))) unsigned short s_dy[LNF_WPB][LNF_MAXH];
+  const int lane = threadIdx.x & (QN_WAVE - 1);
+  const int wave = threadIdx.x / QN_WAVE;
+  const int nchunks = gridDim.x;
+  const int chunk = blockIdx.x;
+  // rows of this chunk: chunk + k * nchunks, k < nk
+  const int nk = chunk < rows ? (rows - chunk + nchunks - 1) / nchunks : 0;
+  const int i0 = lane * 8, i1 = lane * 8 + QN_WAVE * 8;
+
+  float aw = 0.f, ab = 0.f;  // column threadIdx.x
+  s16x8 xq[2] = {{0}, {0}}, dq[2] = {{0}, {0}};  // raw x, dy of the wave's row
+  if (wave < nk) {
+    const long long off = ((long long)chunk + (long long)wave * nchunks) * H;
+    if (i0 < H) {
+      xq[0] = *reinterpret_cast<const s16x8*>(x + off + i0);
+      dq[0] = *reinterpret_cast<const s16x8*>(dy + off + i0);
+    }
+    if (i1 < H) {
+      xq[1] = *reinterpret_cast<const s16x8*>(x + off + i1);
+      dq[1] = *reinterpret_cast<const s16x8*>(dy + off + i1);
+    }
+  }
+
+  for (int k0 = 0; k0 < nk; k0 += LNF_WPB) {
+    const int k = k0 + wave;
+    // next round's row is loaded ahead of this round's barriers
+    s16x8 xn[2] = {xq[0], xq[1]}, dn[2] = {dq[0], dq[1]};
+    if (k + LNF_WPB < nk) {
+      const long long off =
+          ((long long)chunk + (long long)(k + LNF_WPB) * nchunks) * H;
+      if (i0 < H) {
+        xn[0] = *reinterpret_cast<const s16x8*>(x + off + i0);
+        dn[0] = *reinterpret_cast<const s16x8*>(dy + off + i0);
+      }
+      if (i1 < H) {
+        xn[1] = *reinterpret_cast<const s16x8*>(x + off + i1);
+        dn[1] = *reinterpret_cast<const s16x8*>(dy + off + i1);
+      }
+    }
+    if (k < nk) {
+      const long long row = (long long)chunk + (long long)k * nchunks;
+      const unsigned short* dsr = dsum ? dsum + row * H : nullptr;
+      unsigned short* dxr = dx + row * H;
+      const float mean = mean_in[row], rstd = rstd_in[row];
+
+      float cx[16], cwdy[16];
+      float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int i = kk == 0 ? i0 : i1;
+        if (i < H) {
+          float wv[8];
+          ld8_f32(w + i, wv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float xhat = (bf16_to_f32((unsigned short)xq[kk][j]) - mean) * rstd;
+            float wdy = wv[j] * bf16_to_f32((unsigned short)dq[kk][j]);
+            cx[kk * 8 + j] = xhat; cwdy[kk * 8 + j] = wdy;
+            c1 += wdy;
+            // as compiled, layernorm_bwd_dx_kernel fuses only the first
+            // product of each 8-group into an fma (the other seven are
+            // packed multiplies followed by adds)
+            c2 = j == 0 ? __builtin_fmaf(wdy, xhat, c2) : c2 + wdy * xhat;
+            s_xhat[wave][i + j] = xhat;
+          }
+          *reinterpret_cast<s16x8*>(&s_dy[wave][i]) = dq[kk];
+        }
+      }
+      c1 = wave_reduce_sum(c1) / H;
+      c2 = wave_reduce_sum(c2) / H;
+
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int i = kk == 0 ? i0 : i1;
+        if (i < H) {
+          float ov[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            ov[j] = __builtin_fmaf(-cx[kk * 8 + j], c2, cwdy[kk * 8 + j] - c1) * rstd;
+          if (dsr) {
+            float dsv[8];
+            ld8_f32(dsr + i, dsv);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) ov[j] += dsv[j];
+          }
+          st8_f32(dxr + i, ov);
+        }
+      }
+    }
+    __syncthreads();
+    // column sums in row order: aw += dy * xhat (rounded product), ab += dy
+    const int nact = min(LNF_WPB, nk - k0);
+    if ((int)threadIdx.x < H) {
+      for (int r = 0; r < nact; ++r) {
+        const float d = bf16_to_f32(s_dy[r][threadIdx.x]);
+        aw = aw + s_xhat[r][threadIdx.x] * d;
+        ab = ab + d;
+      }
+    }
+    __syncthreads();
+    xq[0] = xn[0]; xq[1] = xn[1]; dq[0] = dn[0]; dq[1] = dn[1];
+  }
+  // [chunks, H] partials, the layout layernorm_bwd_dwdb_kernel writes
+  if ((int)threadIdx.x < H) {
+    dw[(long long)chunk * H + threadIdx.x] = aw;
+    db[(long long)chunk * H + threadIdx.x] = ab;
+  }
+}
+
+bool layernorm_bwd_fused_shape_ok(int H) {
+  return (H & 7) == 0 && H >= 512 && H <= LNF_MAXH;
+}
+
+// dw, db: [layernorm_bwd_chunks(rows), H] partials each, as for
+// layernorm_bwd_launch.  Pointers must be 16-byte aligned.
+void layernorm_bwd_fused_launch(const unsigned short* dy, const unsigned short* x,
+                                const unsigned short* w, const float* mean,
+                                const float* rstd, const unsigned short* dsum,
+                                unsigned short* dx, float* dw, float* db,
+                                int rows, int H, hipStream_t stream) {
+  hipLaunchKernelGGL(layernorm_bwd_fused_kernel, dim3(layernorm_bwd_chunks(rows)),
+                     dim3(LNF_WPB * QN_WAVE), 0, stream, dy, x, w, mean, rstd,
+                     dsum, dx, dw, db, rows, H);
+}
 
 // ---- launchers -------------------------------------------------------------
 template <typename T>
