@@ -1,6 +1,7 @@
 """Serving decode benchmark: KV-cached autoregressive generation.
 
 GPU:  python bench_decode.py [--batch 1,8,32] [--new 64] [--prompt 128]
+                             [--no-fused-attn]
 Reports decode tokens/s per batch size (GPT-2 124M, bf16, int8-cache
 variant included).
 """
@@ -15,6 +16,9 @@ def main():
     ap.add_argument("--batch", type=str, default="1,8,32")
     ap.add_argument("--new", type=int, default=64)
     ap.add_argument("--prompt", type=int, default=128)
+    ap.add_argument("--no-fused-attn", action="store_true",
+                    help="graph line with the composed torch attention "
+                         "instead of the fused decode-attention kernel")
     args = ap.parse_args()
 
     from quintnet_amd.models import GPT2Config, GPT2Stage
@@ -42,7 +46,8 @@ def main():
                   flush=True)
         # hipGraph-captured static-cache decode (one replay per token)
         dec = StaticKVDecoder(model, batch=bs,
-                              max_len=args.prompt + args.new + 8)
+                              max_len=args.prompt + args.new + 8,
+                              fused_attention=False if args.no_fused_attn else None)
         dec.generate(ids, max_new_tokens=4)  # prefill + capture warmup
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -56,8 +61,9 @@ def main():
         ref = model.generate(ids, max_new_tokens=8)
         eq = "ok" if torch.equal(out[:, : args.prompt + 8],
                                  ref[:, : args.prompt + 8]) else "MISMATCH"
+        attn = "fused-attn" if dec.fused_attention else "composed-attn"
         print(f"bs={bs:<3} graph : {ntok / dt:8.1f} tok/s "
-              f"({dt / args.new * 1e3:.2f} ms/token) {eq}", flush=True)
+              f"({dt / args.new * 1e3:.2f} ms/token) {eq} [{attn}]", flush=True)
 
 
 if __name__ == "__main__":

@@ -71,6 +71,14 @@ void attn_bwd_dkv_launch(const unsigned short*, const unsigned short*, const uns
                          unsigned short*, int, int, int, int, int, float, int, const AttnStrides&,
                          long long, long long, long long, long long, long long, long long,
                          long long, long long, long long, hipStream_t);
+struct DecodeStrides {
+  long long qB, qH, qT, kB, kH, kT, vB, vH, vT, oB, oH, oT;
+};
+long long attn_decode_workspace(int B, int H, int T, int Tmax);
+void attn_decode_launch(const unsigned short*, const unsigned short*, const unsigned short*,
+                        unsigned short*, unsigned short*, const long long*, float*,
+                        unsigned short*, int, int, int, int, float,
+                        const DecodeStrides&, hipStream_t);
 
 namespace {
 
@@ -565,6 +573,43 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                       dv.stride(1), dv.stride(2), cur_stream());
 }
 
+// fused decode attention over a static KV cache: append k_new/v_new at cache
+// rows [past, past+T) and attend row r over rows [0, past+r].  `past` stays on
+// the device (no host read, no sync), so the call can be graph-captured.
+void attn_decode(torch::Tensor q, torch::Tensor k_new, torch::Tensor v_new,
+                 torch::Tensor kc, torch::Tensor vc, torch::Tensor past,
+                 torch::Tensor out, double scale) {
+  int64_t B = q.size(0), H = q.size(1), T = q.size(2);
+  TORCH_CHECK(T >= 1 && T <= 8, "attn_decode: 1 <= T <= 8 query rows");
+  check_attn_view(q, B, H, T); check_attn_view(k_new, B, H, T);
+  check_attn_view(v_new, B, H, T); check_attn_view(out, B, H, T);
+  TORCH_CHECK(kc.dim() == 4 && kc.size(2) >= 1, "attn_decode: bad cache shape");
+  int64_t Tmax = kc.size(2);
+  check_attn_view(kc, B, H, Tmax); check_attn_view(vc, B, H, Tmax);
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(),
+              "attn_decode: caches must be contiguous [B,H,Tmax,64]");
+  TORCH_CHECK(Tmax <= (1 << 24), "attn_decode: Tmax too large");
+  for (const torch::Tensor* t : {&q, &k_new, &v_new, &kc, &vc, &out}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == past.device(),
+                "attn_decode: all tensors must be on the GPU that holds past");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "attn_decode: views must be 16B-aligned");
+  }
+  TORCH_CHECK(past.is_cuda() && past.dtype() == torch::kInt64 && past.numel() == 1,
+              "attn_decode: past must be a one-element int64 GPU tensor");
+  auto work = torch::empty(
+      {attn_decode_workspace((int)B, (int)H, (int)T, (int)Tmax)},
+      q.options().dtype(torch::kFloat32));
+  DecodeStrides st{q.stride(0), q.stride(1), q.stride(2), k_new.stride(0),
+                   k_new.stride(1), k_new.stride(2), v_new.stride(0),
+                   v_new.stride(1), v_new.stride(2), out.stride(0),
+                   out.stride(1), out.stride(2)};
+  attn_decode_launch(ap(q), ap(k_new), ap(v_new), ap_mut(kc), ap_mut(vc),
+                     reinterpret_cast<const long long*>(past.data_ptr<int64_t>()),
+                     work.data_ptr<float>(), ap_mut(out), (int)B, (int)H, (int)T,
+                     (int)Tmax, (float)scale, st, cur_stream());
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -595,6 +640,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dout"), py::arg("lse2"), py::arg("dq"), py::arg("dk"),
         py::arg("dv"), py::arg("scale"), py::arg("causal"),
         py::arg("q_offset") = 0);
+  m.def("attn_decode", &attn_decode,
+        "fused decode attention over a static KV cache (D=64, 1..8 rows)",
+        py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("kc"),
+        py::arg("vc"), py::arg("past"), py::arg("out"), py::arg("scale"));
   m.def("adamw_step", &adamw_step);
   m.def("gemm_bias_gelu_aux", &gemm_bias_gelu_aux,
         "hipBLASLt GEMM + fused bias/GELU epilogue (aux = pre-activation)");

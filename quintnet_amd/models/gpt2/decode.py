@@ -14,10 +14,12 @@ Greedy only (sampling needs host RNG), pp == 1, tp == 1.
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
 
+from ...ops.attention import decode_attention, decode_attention_native_ok
 from .config import GPT2Config
 from .stage import GPT2Stage
 
@@ -25,7 +27,12 @@ __all__ = ["StaticKVDecoder"]
 
 
 class StaticKVDecoder:
-    def __init__(self, stage: GPT2Stage, batch: int, max_len: Optional[int] = None):
+    def __init__(self, stage: GPT2Stage, batch: int, max_len: Optional[int] = None,
+                 fused_attention: Optional[bool] = None):
+        """``fused_attention``: None = auto (the fused decode-attention
+        kernel wherever it runs natively for this stage), False = the
+        composed torch sequence, True = always go through
+        ops.decode_attention.  ``QN_DECODE_ATTN=0`` forces it off."""
         assert stage.is_first_stage and stage.is_last_stage, "pp==1 only"
         assert stage.tp_group is None, "graph decode: tp==1 only"
         self.stage = stage
@@ -48,6 +55,11 @@ class StaticKVDecoder:
         self._graph = None
         self._dev = dev
         self._dt = dt
+        if os.environ.get("QN_DECODE_ATTN") == "0":
+            fused_attention = False
+        elif fused_attention is None:
+            fused_attention = decode_attention_native_ok(dev, dt, D)
+        self.fused_attention = bool(fused_attention)
 
     # ------------------------------------------------------------------
     def _block_step(self, i: int, x: torch.Tensor, t0: torch.Tensor,
@@ -66,7 +78,16 @@ class StaticKVDecoder:
         q = heads(qkv[:, :, :hl])
         k = heads(qkv[:, :, hl : 2 * hl])
         v = heads(qkv[:, :, 2 * hl :])
-        idx = t0 + torch.arange(T, device=x.device)
+        if self.fused_attention and T <= 8:
+            # one fused append + attend (ops.decode_attention); reads the
+            # qkv views in place and writes the [B, T, H*D] layout c_proj wants
+            out = qkv.new_empty(B, T, hl)
+            decode_attention(q, k, v, self.kc[i], self.vc[i], t0,
+                             out=out.view(B, T, H, D).permute(0, 2, 1, 3))
+            x = x + blk.attn.resid_dropout(blk.attn.c_proj(out))
+            x = x + blk.mlp(blk.ln_2(x))
+            return x
+        idx =t0 + torch.arange(T, device=x.device)
         self.kc[i].index_copy_(2, idx, k)
         self.vc[i].index_copy_(2, idx, v)
         scale = 1.0 / (D ** 0.5)

@@ -16,6 +16,7 @@ from .attention import (
     FlashAttentionFunction,
     causal_softmax,
     softmax_bwd,
+    decode_attention,
 )
 from .cross_entropy import cross_entropy, causal_lm_loss, shift_labels, CrossEntropyFunction
 from .adamw import (
@@ -47,6 +48,7 @@ __all__ = [
     "FlashAttentionFunction",
     "causal_softmax",
     "softmax_bwd",
+    "decode_attention",
     "cross_entropy",
     "causal_lm_loss",
     "shift_labels",

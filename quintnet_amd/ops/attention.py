@@ -21,7 +21,13 @@ import torch
 
 from . import _backend
 
-__all__ = ["attention", "AttentionFunction", "causal_softmax", "softmax_bwd"]
+__all__ = [
+    "attention",
+    "AttentionFunction",
+    "causal_softmax",
+    "softmax_bwd",
+    "decode_attention",
+]
 
 
 def causal_softmax(
@@ -236,3 +242,93 @@ def attention_qkv(qkv: torch.Tensor, n_heads: int, causal: bool = True) -> torch
 
     out = attention(heads(q), heads(k), heads(v), causal=causal)
     return out.transpose(1, 2).reshape(B, T, hl)
+
+
+def _decode_view_ok(t: torch.Tensor) -> bool:
+    return (
+        t.stride(-1) == 1
+        and all(s % 8 == 0 for s in t.stride()[:-1])
+        and t.data_ptr() % 16 == 0
+    )
+
+
+def decode_attention_native_ok(
+    device: torch.device, dtype: torch.dtype, head_dim: int
+) -> bool:
+    """Whether decode_attention runs the fused HIP kernel for tensors of
+    this device/dtype/head_dim (given 1 <= T <= 8 and eligible strides).
+    On a GPU a missing extension raises instead of answering False."""
+    if _backend.force_eager() or device.type != "cuda":
+        return False
+    if dtype != torch.bfloat16 or head_dim != 64:
+        return False
+    _backend.ext()
+    return True
+
+
+def decode_attention(
+    q: torch.Tensor,
+    k_new: torch.Tensor,
+    v_new: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    past,
+    out: torch.Tensor = None,
+) -> torch.Tensor:
+    """Append-and-attend over a static KV cache (the decode hot op).
+
+    q, k_new, v_new: [B, H, T, D] (views of the packed c_attn output are
+    fine); k_cache, v_cache: contiguous [B, H, Tmax, D]; ``past``: the
+    number of rows already cached — a 0-dim int64 tensor on the caches'
+    device (or a host int, which is range-checked here).  Writes k_new/v_new into cache
+    rows [past, past+T), then query row r attends rows [0, past+r].
+    Returns the [B, H, T, D] result (``out`` if given, else a view of a
+    fresh [B, T, H*D] buffer, the layout c_proj wants).
+
+    On gfx950 (bf16, D == 64, 1 <= T <= 8, 16-byte-aligned strides) this is
+    one fused split-KV kernel plus a combine (csrc/attn_decode.hip): past
+    is read on the device, so there is no host sync and the call can sit in
+    a captured graph; work follows ``past``, not Tmax.  Elsewhere it is the
+    composed sequence over the whole cache, masked by position.
+    """
+    B, H, T, D = q.shape
+    Tmax = k_cache.shape[2]
+    assert k_new.shape == q.shape and v_new.shape == q.shape
+    assert k_cache.shape == (B, H, Tmax, D) and v_cache.shape == k_cache.shape
+    host_past = None
+    if isinstance(past, int):
+        host_past = past
+    elif not past.is_cuda:
+        host_past = int(past)
+    if host_past is not None:
+        assert 0 <= host_past and host_past + T <= Tmax, (
+            f"decode_attention: rows [{host_past}, {host_past + T}) do not "
+            f"fit a cache of {Tmax}"
+        )
+    if out is None:
+        out = q.new_empty(B, T, H, D).permute(0, 2, 1, 3)
+    assert out.shape == q.shape
+    scale = 1.0 / (D ** 0.5)
+    if (
+        T <= 8
+        and decode_attention_native_ok(q.device, q.dtype, D)
+        and all(_decode_view_ok(t) for t in (q, k_new, v_new, out))
+    ):
+        if host_past is not None:  # a host value: no device read involved
+            past = torch.tensor(host_past, dtype=torch.long, device=q.device)
+        _backend.ext().attn_decode(q, k_new, v_new, k_cache, v_cache, past, out, scale)
+        return out
+    # composed path: the arithmetic StaticKVDecoder used before the fused
+    # kernel, kept bit-for-bit (CPU results must not move)
+    rows = torch.arange(T, device=q.device)
+    idx = past + rows
+    k_cache.index_copy_(2, idx, k_new)
+    v_cache.index_copy_(2, idx, v_new)
+    scores = torch.matmul(q, k_cache.transpose(-2, -1)).float() * scale
+    qpos = (past + rows).view(1, 1, T, 1)
+    pos = torch.arange(Tmax, device=q.device)
+    visible = pos.view(1, 1, 1, -1) <= qpos
+    scores = scores.masked_fill(~visible, float("-inf"))
+    p = torch.softmax(scores, dim=-1).to(q.dtype)
+    out.copy_(torch.matmul(p, v_cache))
+    return out
