@@ -29,8 +29,21 @@
 // the fwd (lane-owns-q) orientation; dkv uses the mirrored
 // (lane-owns-key) orientation so dK^T/dV^T accumulate lane-locally.
 //
+// One kernel body per pass.  The occupancy variants are template
+// instantiations picked by the launchers from an environment knob:
+//   attn_fwd_kernel<MINW, KLDS>      QN_ATTN_FWD_OCC (3 | 4), QN_ATTN_KLDS (1 | 0)
+//   attn_bwd_dq_kernel<MINW, PIPE>   QN_ATTN_DQ_OCC  (3 | 2 pipelined, 4 not)
+//   attn_bwd_dkv_kernel<MINW, PIPE>  QN_ATTN_DKV_OCC (2 pipelined, 3 not)
+// The passes share the leaf helpers below (row images, S/dP chain,
+// transposed-tile MFMAs, scatter store, q-major causal window) and take
+// their tensors as pointer + AttnView strides (attn.h).
+// tests/test_attention_variants_gpu.py runs every instantiation.
+//
 // Replaces reference F.scaled_dot_product_attention
 // (utils/GPT2/gpt2_attention.py:156).
+#include <cstdlib>
+
+#include "attn.h"
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -106,19 +119,11 @@ __device__ __forceinline__ int drow(int r, int lane) {
   return (r & 3) + ((r >> 2) << 3) + ((lane >> 5) << 2);
 }
 
-// cooperative transpose-stage of a [rows<=32, 64] strided tile into
-// LDS t[64][TPAD] (t[d][r]); 256 threads, 8 contiguous elems each.
-// Split into load (issue early, overlap with compute — T14) and write.
+// cooperative transpose-stage of a [32, 64] strided tile into LDS
+// t[64][TPAD] (t[d][r]); 256 threads, 8 contiguous elems each.  Split
+// into load (stage_at: issue early, overlap with compute — T14) and write.
 // thread -> (row, d-chunk) map r = t&31, d0 = (t>>5)*8: the ds_write_u16
 // bank pattern is then 4-way (r spreads banks) instead of 16-way.
-__device__ __forceinline__ s16x8 stage_ld(const unsigned short* src,
-                                          long long row_stride, int row0) {
-  int r = threadIdx.x & 31;
-  int d0 = (threadIdx.x >> 5) << 3;
-  const unsigned short* p = src + (long long)(row0 + r) * row_stride + d0;
-  return *reinterpret_cast<const s16x8*>(p);
-}
-
 __device__ __forceinline__ void stage_wr(unsigned short* t, s16x8 v) {
   int r = threadIdx.x & 31;
   int d0 = (threadIdx.x >> 5) << 3;
@@ -126,10 +131,74 @@ __device__ __forceinline__ void stage_wr(unsigned short* t, s16x8 v) {
   for (int j = 0; j < 8; ++j) t[(d0 + j) * TPAD + r] = (unsigned short)v[j];
 }
 
-__device__ __forceinline__ void stage_transpose(
-    unsigned short* t, const unsigned short* src, long long row_stride,
-    int row0, int nrows) {
-  if ((threadIdx.x & 31) < nrows) stage_wr(t, stage_ld(src, row_stride, row0));
+// ---- row images: [32][KPAD] row-major LDS copies of a staged tile ---------
+// The block-shared MFMA operands are read from these as b128 fragments;
+// stride 72 keeps those reads bank-conflict-free.  Both offsets are
+// loop-invariant: each kernel computes them once.
+#define KPAD 72
+
+// this thread's 8 staged elements (same row/d-chunk map as stage_wr)
+__device__ __forceinline__ int rowimg_st_off() {
+  return (threadIdx.x & 31) * KPAD + ((threadIdx.x >> 5) << 3);
+}
+
+// this lane's kt=0 A/B fragment; kt = 1..3 sit at +16 elems
+__device__ __forceinline__ int rowimg_frag_off(int lane) {
+  return (lane & 31) * KPAD + ((lane >> 5) << 3);
+}
+
+__device__ __forceinline__ void rowimg_st(unsigned short* img, int st_off, s16x8 v) {
+  *reinterpret_cast<s16x8*>(img + st_off) = v;
+}
+
+// S and dP for one 32x32 tile: s = A·x, dp = B·y over D = 64, the two
+// chains interleaved.  a/b point at this lane's fragment in two row
+// images, x/y are the wave's register fragments: dq passes the K/V images
+// with its Q/dO fragments, dkv the Q/dO images with its K/V fragments.
+__device__ __forceinline__ void sdp_chain(
+    const unsigned short* a, const unsigned short* b, const bf16x8 (&x)[4],
+    const bf16x8 (&y)[4], const f32x16& zc, f32x16& s, f32x16& dp) {
+  s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_at(a, 0), x[0], zc, 0, 0, 0);
+  dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_at(b, 0), y[0], zc, 0, 0, 0);
+#pragma unroll
+  for (int t = 1; t < 4; ++t) {
+    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_at(a, t), x[t], s, 0, 0, 0);
+    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_at(b, t), y[t], dp, 0, 0, 0);
+  }
+}
+
+// acc^T[mt*32 + .][col] += t[mt*32 + .][0..32) · (b0 | b1): the A operand
+// is rows mt*32.. of a transposed tile t[64][TPAD], b0/b1 the relayouted
+// fragments of the tile's two 16-row halves.  One accumulator by
+// reference per call — an accumulator ARRAY passed by pointer spills.
+__device__ __forceinline__ void tmfma2(const unsigned short* t, int mt, int lane,
+                                       bf16x8 b0, bf16x8 b1, f32x16& acc) {
+  const unsigned short* a = &t[(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_at(a, 0), b0, acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_at(a, 1), b1, acc, 0, 0, 0);
+}
+
+// scatter-store half mt of a transposed accumulator (lane owns one output
+// row, its registers are d = mt*32 + drow(r)) into that row as bf16
+__device__ __forceinline__ void drow_st(unsigned short* row, int mt, int lane, f32x16 acc) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) row[mt * 32 + drow(r, lane)] = f32_to_bf16(acc[r]);
+}
+
+// ---- causal window, q-major loops (fwd, dq): block owns q rows
+// [q0, q0+128), wave rows [qw, qw+32), and walks 32-key tiles at kv0.
+// q rows are local [0,Tq); their GLOBAL positions are +qoff (context
+// parallelism: K/V cover the full sequence [0,Tk), Q is this rank's shard).
+__device__ __forceinline__ int qmajor_kv_end(bool causal, int q0, int qoff, int Tk) {
+  return causal ? min(q0 + qoff + 128, Tk) : Tk;
+}
+// the wave has at least one visible (q, key) pair in the tile
+__device__ __forceinline__ bool qmajor_active(bool causal, int kv0, int qw, int qoff) {
+  return !causal || kv0 <= qw + qoff + 31;
+}
+// the tile crosses the diagonal: only then is the per-element mask needed
+__device__ __forceinline__ bool qmajor_diag(bool causal, int kv0, int qw, int qoff) {
+  return causal && (kv0 + 31 > qw + qoff);
 }
 
 // ===========================================================================
@@ -138,18 +207,12 @@ __device__ __forceinline__ void stage_transpose(
 // q/k/v strided [.., T, 64] slices; out written via its own strides
 // (so [B, T, H*64] layout comes out directly); lse2 [BH, T] f32.
 // ===========================================================================
-#define KPAD 72  // K-tile LDS row stride (elems): conflict-free b128 frags
-
-template <int MINW, bool KLDS = false>
+template <int MINW, bool KLDS>
 __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v, unsigned short* __restrict__ out,
     float* __restrict__ lse2, int Tq, int Tk, int qoff, int H, float scale,
-    int causal,
-    long long qsB, long long qsH, long long qsT,
-    long long ksB, long long ksH, long long ksT,
-    long long vsB, long long vsH, long long vsT,
-    long long osB, long long osH, long long osT) {
+    int causal, AttnView qs, AttnView ks, AttnView vs, AttnView os) {
   __shared__ unsigned short vt[64 * TPAD + (KLDS ? 32 * KPAD : 0)];
   unsigned short* klds = vt + 64 * TPAD;  // [32][KPAD] row-major K tile
   const int bh = blockIdx.y;
@@ -160,15 +223,15 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
   const int qw = q0 + wave * 32;          // wave q range  [qw, qw+32)
   const int myq = qw + (lane & 31);       // this lane's q row
 
-  const unsigned short* qp = q + b * qsB + h * qsH;
-  const unsigned short* kp = k + b * ksB + h * ksH;
-  const unsigned short* vp = v + b * vsB + h * vsH;
-  unsigned short* op = out + b * osB + h * osH;
+  const unsigned short* qp = q + b * qs.B + h * qs.H;
+  const unsigned short* kp = k + b * ks.B + h * ks.H;
+  const unsigned short* vp = v + b * vs.B + h * vs.H;
+  unsigned short* op = out + b * os.B + h * os.H;
 
   // Q fragments (B-operand): held in regs for the whole kernel
   bf16x8 qf[4];
 #pragma unroll
-  for (int kt = 0; kt < 4; ++kt) qf[kt] = frag_ld(qp, qsT, qw, kt * 16, lane);
+  for (int kt = 0; kt < 4; ++kt) qf[kt] = frag_ld(qp, qs.T, qw, kt * 16, lane);
 
   float m2 = -INFINITY, l = 0.f;
   f32x16 o[2];
@@ -179,18 +242,17 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
   for (int i = 0; i < 16; ++i) zc[i] = 0.f;
 
   const float s2scale = scale * LOG2E;
-  // q rows are local [0,Tq); their GLOBAL positions are +qoff (context
-  // parallelism: K/V cover the full sequence [0,Tk), Q is this rank's shard)
-  const int kv_end = causal ? min(q0 + qoff + 128, Tk) : Tk;
+  const int kv_end = qmajor_kv_end(causal, q0, qoff, Tk);
+  const int st_off = rowimg_st_off(), fr_off = rowimg_frag_off(lane);  // KLDS
 
   // prefetch pipeline: tile t's K fragments + V staging rows load during
   // tile t-1's MFMA cluster (T14) — the per-iteration global latency was
   // the dominant cost of the unpipelined version.  Source addresses are
   // pointer-bumped (+= 32 rows per tile), never rebuilt.
-  const unsigned short* kfp = frag_base(kp, ksT, 0, lane);
-  const unsigned short* ksp = stage_base(kp, ksT, 0);   // KLDS path
-  const unsigned short* vsp = stage_base(vp, vsT, 0);
-  const long long kstep = 32 * ksT, vstep = 32 * vsT;
+  const unsigned short* kfp = frag_base(kp, ks.T, 0, lane);
+  const unsigned short* ksp = stage_base(kp, ks.T, 0);   // KLDS path
+  const unsigned short* vsp = stage_base(vp, vs.T, 0);
+  const long long kstep = 32 * ks.T, vstep = 32 * vs.T;
   bf16x8 kf_n[4];
   s16x8 v_n = stage_at(vsp);
   s16x8 k_n = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -205,21 +267,14 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
     // cooperative V^T (+ row-major K) staging: write the prefetched rows
     __syncthreads();
     stage_wr(vt, v_n);
-    if constexpr (KLDS) {
-      // [row][KPAD] image, 16B-aligned s16x8 stores
-      int r = threadIdx.x & 31;
-      int d0 = (threadIdx.x >> 5) << 3;
-      *reinterpret_cast<s16x8*>(klds + r * KPAD + d0) = k_n;
-    }
+    if constexpr (KLDS) rowimg_st(klds, st_off, k_n);
     __syncthreads();
 
     bf16x8 kf_c[4];
     if constexpr (KLDS) {
-      // shared K fragments from LDS (stride 72: conflict-free)
-      const unsigned short* kl = klds + (lane & 31) * KPAD + ((lane >> 5) << 3);
+      // shared K fragments from the LDS row image
 #pragma unroll
-      for (int kt = 0; kt < 4; ++kt)
-        kf_c[kt] = *reinterpret_cast<const bf16x8*>(kl + kt * 16);
+      for (int kt = 0; kt < 4; ++kt) kf_c[kt] = frag_at(klds + fr_off, kt);
     } else {
 #pragma unroll
       for (int kt = 0; kt < 4; ++kt) kf_c[kt] = kf_n[kt];
@@ -237,7 +292,7 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
       }
     }
 
-    if (!causal || kv0 <= qw + qoff + 31) {  // wave has >= one valid pair
+    if (qmajor_active(causal, kv0, qw, qoff)) {
       // S^T[key][q] = sum_d K[key][d] Q[q][d]  (first mfma takes the
       // persistent zero C — no per-tile accumulator re-init)
       f32x16 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf_c[0], qf[0], zc, 0, 0, 0);
@@ -246,7 +301,7 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf_c[kt], qf[kt], s, 0, 0, 0);
       }
       // scale to base-2; causal mask only on the diagonal tile
-      const bool diag = causal && (kv0 + 31 > qw + qoff);
+      const bool diag = qmajor_diag(causal, kv0, qw, qoff);
       float ps[16];
       float pmax = -INFINITY;
       if (diag) {
@@ -292,13 +347,7 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
       bf16x8 pf1 = relayout8(ps + 8);
       // O^T[d][q] += V^T · P : A from vt
 #pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const unsigned short* av = &vt[(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(av);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(av + 16);
-        o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, pf0, o[mt], 0, 0, 0);
-        o[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, pf1, o[mt], 0, 0, 0);
-      }
+      for (int mt = 0; mt < 2; ++mt) tmfma2(vt, mt, lane, pf0, pf1, o[mt]);
     }
   }
 
@@ -306,13 +355,7 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
   float inv = (l > 0.f) ? 1.0f / l : 0.f;
   if (myq < Tq) {
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int d = mt * 32 + drow(r, lane);
-        op[(long long)myq * osT + d] = f32_to_bf16(o[mt][r] * inv);
-      }
-    }
+    for (int mt = 0; mt < 2; ++mt) drow_st(op + (long long)myq * os.T, mt, lane, o[mt] * inv);
     if (lane < 32) lse2[(long long)bh * Tq + myq] = m2 + __log2f(l);
   }
 }
@@ -322,9 +365,8 @@ __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
 // ===========================================================================
 __global__ void attn_delta_kernel(
     const unsigned short* __restrict__ dout, const unsigned short* __restrict__ out,
-    float* __restrict__ delta, long long nrows, int T, int H,
-    long long dsB, long long dsH, long long dsT,
-    long long osB, long long osH, long long osT) {
+    float* __restrict__ delta, long long nrows, int T, int H, AttnView dos,
+    AttnView os) {
   // 4 rows per wave, s16x4 (8B) loads per lane: lane l covers row l>>4,
   // elems (l&15)*4 .. +4 (D = 64)
   const int lane = threadIdx.x & 63;
@@ -336,8 +378,8 @@ __global__ void attn_delta_kernel(
   const int t = (int)(row % T);
   const int bh = (int)(row / T);
   const int b = bh / H, h = bh % H;
-  const unsigned short* dp = dout + b * dsB + h * dsH + (long long)t * dsT + d0;
-  const unsigned short* op = out + b * osB + h * osH + (long long)t * osT + d0;
+  const unsigned short* dp = dout + b * dos.B + h * dos.H + (long long)t * dos.T + d0;
+  const unsigned short* op = out + b * os.B + h * os.H + (long long)t * os.T + d0;
   s16x4 dv = *reinterpret_cast<const s16x4*>(dp);
   s16x4 ov = *reinterpret_cast<const s16x4*>(op);
   float acc = 0.f;
@@ -354,22 +396,30 @@ __global__ void attn_delta_kernel(
 // backward dQ: block owns a 128-row q tile (wave per 32 rows), loops kv.
 // dQ^T[d][q] += K^T[d][key] · g^T[key][q],
 //   g^T = scale * P^T ⊙ (dP^T - delta[q]),  P^T = exp2(s2 - lse2[q])
+//
+// PIPE = true is the shipped form: a cross-tile pipeline — dQ MFMAs of
+// tile i, barrier, then the S/dP MFMAs for tile i+1 from the freshly
+// staged LDS row images, with tile i+2's staging loads in flight.
+// PIPE = false is the non-pipelined form for the 4-waves/SIMD point
+// (QN_ATTN_DQ_OCC=4), the same trade as in attn_bwd_dkv_kernel: the S/dP
+// chains become transient inside the tile (no cross-tile pipelining), the
+// softmax runs 8 values at a time, staging loads issue after the tile's
+// MFMAs, and the extra resident wave hides the latency the in-wave overlap
+// used to.  The pipelined <3> form needs 162 VGPRs; instantiating it at 4
+// waves spills 22.
 // ===========================================================================
-template <int MINW>
+template <int MINW, bool PIPE>
 __global__ __launch_bounds__(256, MINW) void attn_bwd_dq_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
     const float* __restrict__ lse2, const float* __restrict__ delta,
     unsigned short* __restrict__ dq, int Tq, int Tk, int qoff, int H,
-    float scale, int causal,
-    long long qsB, long long qsH, long long qsT,
-    long long ksB, long long ksH, long long ksT,
-    long long vsB, long long vsH, long long vsT,
-    long long dsB, long long dsH, long long dsT,
-    long long dqsB, long long dqsH, long long dqsT) {
+    float scale, int causal, AttnView qs, AttnView ks, AttnView vs, AttnView dos,
+    AttnView dqs) {
+  // double-buffered K^T tile + row-major K/V images: the shared fragment
+  // source for the S/dP MFMAs (replaces 4x-redundant per-wave global
+  // fragment loads)
   __shared__ unsigned short kt_lds[2][64 * TPAD];
-  // row-major K/V tiles: shared fragment source for the S/dP MFMAs
-  // (replaces 4x-redundant per-wave global fragment loads)
   __shared__ unsigned short krow_l[2][32 * KPAD];
   __shared__ unsigned short vrow_l[2][32 * KPAD];
   const int bh = blockIdx.y;
@@ -380,17 +430,17 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dq_kernel(
   const int qw = q0 + wave * 32;
   const int myq = qw + (lane & 31);
 
-  const unsigned short* qp = q + b * qsB + h * qsH;
-  const unsigned short* kp = k + b * ksB + h * ksH;
-  const unsigned short* vp = v + b * vsB + h * vsH;
-  const unsigned short* dop = dout + b * dsB + h * dsH;
-  unsigned short* dqp = dq + b * dqsB + h * dqsH;
+  const unsigned short* qp = q + b * qs.B + h * qs.H;
+  const unsigned short* kp = k + b * ks.B + h * ks.H;
+  const unsigned short* vp = v + b * vs.B + h * vs.H;
+  const unsigned short* dop = dout + b * dos.B + h * dos.H;
+  unsigned short* dqp = dq + b * dqs.B + h * dqs.H;
 
   bf16x8 qf[4], dof[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    qf[t] = frag_ld(qp, qsT, qw, t * 16, lane);
-    dof[t] = frag_ld(dop, dsT, qw, t * 16, lane);
+    qf[t] = frag_ld(qp, qs.T, qw, t * 16, lane);
+    dof[t] = frag_ld(dop, dos.T, qw, t * 16, lane);
   }
   const float my_lse = lse2[(long long)bh * Tq + min(myq, Tq - 1)];
   const float my_delta = delta[(long long)bh * Tq + min(myq, Tq - 1)];
@@ -400,270 +450,129 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dq_kernel(
 #pragma unroll
   for (int i = 0; i < 16; ++i) { dqa[0][i] = 0.f; dqa[1][i] = 0.f; zc[i] = 0.f; }
 
-  const int kv_end = causal ? min(q0 + qoff + 128, Tk) : Tk;
-  // cross-tile pipeline: dQ MFMAs of tile i, barrier, then S/dP MFMAs
-  // for tile i+1 from the freshly staged LDS row images; double-buffered.
-  const unsigned short* ksp = stage_base(kp, ksT, 0);
-  const unsigned short* vsp = stage_base(vp, vsT, 0);
-  const long long kstep = 32 * ksT, vstep = 32 * vsT;
-  const int srow_ = threadIdx.x & 31;
-  const int sd0_ = (threadIdx.x >> 5) << 3;
-  const int fl_ = (lane & 31) * KPAD + ((lane >> 5) << 3);
+  const int kv_end = qmajor_kv_end(causal, q0, qoff, Tk);
+  const unsigned short* ksp = stage_base(kp, ks.T, 0);
+  const unsigned short* vsp = stage_base(vp, vs.T, 0);
+  const long long kstep = 32 * ks.T, vstep = 32 * vs.T;
+  const int st_off = rowimg_st_off(), fr_off = rowimg_frag_off(lane);
 
   // prologue: stage tile 0 (Kt transposed + K/V row images)
   {
     s16x8 k0 = stage_at(ksp);
     s16x8 v0 = stage_at(vsp);
     stage_wr(kt_lds[0], k0);
-    *reinterpret_cast<s16x8*>(&krow_l[0][srow_ * KPAD + sd0_]) = k0;
-    *reinterpret_cast<s16x8*>(&vrow_l[0][srow_ * KPAD + sd0_]) = v0;
+    rowimg_st(krow_l[0], st_off, k0);
+    rowimg_st(vrow_l[0], st_off, v0);
   }
+  // PIPE: tile 1's staging rows, prefetched across tile 0's compute
   s16x8 kst_n = {0, 0, 0, 0, 0, 0, 0, 0}, vst_n = kst_n;
-  if (32 < kv_end) {
-    kst_n = stage_at(ksp + kstep);
-    vst_n = stage_at(vsp + vstep);
+  if constexpr (PIPE) {
+    if (32 < kv_end) {
+      kst_n = stage_at(ksp + kstep);
+      vst_n = stage_at(vsp + vstep);
+    }
   }
   __syncthreads();  // buf0 visible
   f32x16 s, dp_;
-  {
-    const unsigned short* kr = &krow_l[0][fl_];
-    const unsigned short* vr = &vrow_l[0][fl_];
-    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-        *reinterpret_cast<const bf16x8*>(kr), qf[0], zc, 0, 0, 0);
-    dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-        *reinterpret_cast<const bf16x8*>(vr), dof[0], zc, 0, 0, 0);
-#pragma unroll
-    for (int t = 1; t < 4; ++t) {
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(kr + t * 16), qf[t], s, 0, 0, 0);
-      dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(vr + t * 16), dof[t], dp_, 0, 0, 0);
-    }
-  }
+  if constexpr (PIPE) sdp_chain(&krow_l[0][fr_off], &vrow_l[0][fr_off], qf, dof, zc, s, dp_);
 
   int cur = 0;
   for (int kv0 = 0; kv0 < kv_end; kv0 += 32) {
     const bool have_next = kv0 + 32 < kv_end;
-    const bool active = !(causal && kv0 > qw + qoff + 31);
+    const bool active = qmajor_active(causal, kv0, qw, qoff);
 
     bf16x8 gf0, gf1;
     if (active) {
-      const bool diag = causal && (kv0 + 31 > qw + qoff);
-      float g[16];
-      if (diag) {
+      // !PIPE: transient S/dP chains for THIS tile
+      if constexpr (!PIPE)
+        sdp_chain(&krow_l[cur][fr_off], &vrow_l[cur][fr_off], qf, dof, zc, s, dp_);
+      const bool diag = qmajor_diag(causal, kv0, qw, qoff);
+      if constexpr (PIPE) {
+        float g[16];
+        if (diag) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int key = kv0 + drow(r, lane);
-          float p = (key > myq + qoff) ? 0.f
-                                       : __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
-          g[r] = scale * p * (dp_[r] - my_delta);
+          for (int r = 0; r < 16; ++r) {
+            int key = kv0 + drow(r, lane);
+            float p = (key > myq + qoff) ? 0.f
+                                         : __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
+            g[r] = scale * p * (dp_[r] - my_delta);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float p = __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
+            g[r] = scale * p * (dp_[r] - my_delta);
+          }
         }
+        gf0 = relayout8(g);
+        gf1 = relayout8(g + 8);
       } else {
+        // softmax half at a time (8-float g liveness)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          float p = __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
-          g[r] = scale * p * (dp_[r] - my_delta);
+        for (int half = 0; half < 2; ++half) {
+          float g[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            int r = half * 8 + j;
+            float p;
+            if (diag) {
+              int key = kv0 + drow(r, lane);
+              p = (key > myq + qoff)
+                      ? 0.f
+                      : __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
+            } else {
+              p = __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
+            }
+            g[j] = scale * p * (dp_[r] - my_delta);
+          }
+          if (half == 0) gf0 = relayout8(g); else gf1 = relayout8(g);
         }
       }
-      gf0 = relayout8(g);
-      gf1 = relayout8(g + 8);
     }
 
-    if (have_next) {
-      stage_wr(kt_lds[cur ^ 1], kst_n);
-      *reinterpret_cast<s16x8*>(&krow_l[cur ^ 1][srow_ * KPAD + sd0_]) = kst_n;
-      *reinterpret_cast<s16x8*>(&vrow_l[cur ^ 1][srow_ * KPAD + sd0_]) = vst_n;
-      ksp += kstep;
-      vsp += vstep;
-      if (kv0 + 64 < kv_end) {
+    if constexpr (PIPE) {
+      if (have_next) {
+        stage_wr(kt_lds[cur ^ 1], kst_n);
+        rowimg_st(krow_l[cur ^ 1], st_off, kst_n);
+        rowimg_st(vrow_l[cur ^ 1], st_off, vst_n);
+        ksp += kstep;
+        vsp += vstep;
+        if (kv0 + 64 < kv_end) {
+          kst_n = stage_at(ksp + kstep);
+          vst_n = stage_at(vsp + vstep);
+        }
+      }
+    }
+
+    if (active) {
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) tmfma2(kt_lds[cur], mt, lane, gf0, gf1, dqa[mt]);
+    }
+
+    if constexpr (!PIPE) {
+      if (have_next) {
+        // stage tile i+1 (loads issued after the MFMAs — registers are
+        // not live across compute; the 4th wave hides the latency)
         kst_n = stage_at(ksp + kstep);
         vst_n = stage_at(vsp + vstep);
-      }
-    }
-
-    if (active) {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const unsigned short* ak = &kt_lds[cur][(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ak);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ak + 16);
-        dqa[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, gf0, dqa[mt], 0, 0, 0);
-        dqa[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, gf1, dqa[mt], 0, 0, 0);
+        stage_wr(kt_lds[cur ^ 1], kst_n);
+        rowimg_st(krow_l[cur ^ 1], st_off, kst_n);
+        rowimg_st(vrow_l[cur ^ 1], st_off, vst_n);
+        ksp += kstep;
+        vsp += vstep;
       }
     }
     __syncthreads();  // buf[cur^1] writes visible; buf[cur] reads done
-    if (have_next) {
-      const unsigned short* kr = &krow_l[cur ^ 1][fl_];
-      const unsigned short* vr = &vrow_l[cur ^ 1][fl_];
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(kr), qf[0], zc, 0, 0, 0);
-      dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(vr), dof[0], zc, 0, 0, 0);
-#pragma unroll
-      for (int t = 1; t < 4; ++t) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(kr + t * 16), qf[t], s, 0, 0, 0);
-        dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(vr + t * 16), dof[t], dp_, 0, 0, 0);
-      }
+    if constexpr (PIPE) {
+      if (have_next)
+        sdp_chain(&krow_l[cur ^ 1][fr_off], &vrow_l[cur ^ 1][fr_off], qf, dof, zc, s, dp_);
     }
     cur ^= 1;
   }
 
   if (myq < Tq) {
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int d = mt * 32 + drow(r, lane);
-        dqp[(long long)myq * dqsT + d] = f32_to_bf16(dqa[mt][r]);
-      }
-  }
-}
-
-// Non-pipelined dq variant for the 4-waves/SIMD point
-// (QN_ATTN_DQ_OCC=4): same trade as attn_bwd_dkv_np_kernel — the S/dP
-// chains become transient inside the tile (no cross-tile pipelining),
-// staging loads issue after the tile's MFMAs, and the extra resident
-// wave hides the latency the in-wave overlap used to.  The pipelined
-// <3> form needs 162 VGPRs; instantiating it at 4 waves spills 22.
-__global__ __launch_bounds__(256, 4) void attn_bwd_dq_np_kernel(
-    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
-    const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
-    const float* __restrict__ lse2, const float* __restrict__ delta,
-    unsigned short* __restrict__ dq, int Tq, int Tk, int qoff, int H,
-    float scale, int causal,
-    long long qsB, long long qsH, long long qsT,
-    long long ksB, long long ksH, long long ksT,
-    long long vsB, long long vsH, long long vsT,
-    long long dsB, long long dsH, long long dsT,
-    long long dqsB, long long dqsH, long long dqsT) {
-  __shared__ unsigned short kt_lds[2][64 * TPAD];
-  __shared__ unsigned short krow_l[2][32 * KPAD];
-  __shared__ unsigned short vrow_l[2][32 * KPAD];
-  const int bh = blockIdx.y;
-  const int b = bh / H, h = bh % H;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int q0 = blockIdx.x * 128;
-  const int qw = q0 + wave * 32;
-  const int myq = qw + (lane & 31);
-
-  const unsigned short* qp = q + b * qsB + h * qsH;
-  const unsigned short* kp = k + b * ksB + h * ksH;
-  const unsigned short* vp = v + b * vsB + h * vsH;
-  const unsigned short* dop = dout + b * dsB + h * dsH;
-  unsigned short* dqp = dq + b * dqsB + h * dqsH;
-
-  bf16x8 qf[4], dof[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    qf[t] = frag_ld(qp, qsT, qw, t * 16, lane);
-    dof[t] = frag_ld(dop, dsT, qw, t * 16, lane);
-  }
-  const float my_lse = lse2[(long long)bh * Tq + min(myq, Tq - 1)];
-  const float my_delta = delta[(long long)bh * Tq + min(myq, Tq - 1)];
-  const float s2scale = scale * LOG2E;
-
-  f32x16 dqa[2], zc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { dqa[0][i] = 0.f; dqa[1][i] = 0.f; zc[i] = 0.f; }
-
-  const int kv_end = causal ? min(q0 + qoff + 128, Tk) : Tk;
-  const unsigned short* ksp = stage_base(kp, ksT, 0);
-  const unsigned short* vsp = stage_base(vp, vsT, 0);
-  const long long kstep = 32 * ksT, vstep = 32 * vsT;
-  const int srow_ = threadIdx.x & 31;
-  const int sd0_ = (threadIdx.x >> 5) << 3;
-  const int fl_ = (lane & 31) * KPAD + ((lane >> 5) << 3);
-
-  {
-    s16x8 k0 = stage_at(ksp);
-    s16x8 v0 = stage_at(vsp);
-    stage_wr(kt_lds[0], k0);
-    *reinterpret_cast<s16x8*>(&krow_l[0][srow_ * KPAD + sd0_]) = k0;
-    *reinterpret_cast<s16x8*>(&vrow_l[0][srow_ * KPAD + sd0_]) = v0;
-  }
-  __syncthreads();  // buf0 visible
-
-  int cur = 0;
-  for (int kv0 = 0; kv0 < kv_end; kv0 += 32) {
-    const bool have_next = kv0 + 32 < kv_end;
-    const bool active = !(causal && kv0 > qw + qoff + 31);
-
-    if (active) {
-      // transient S/dP chains for THIS tile
-      f32x16 s, dp_;
-      {
-        const unsigned short* kr = &krow_l[cur][fl_];
-        const unsigned short* vr = &vrow_l[cur][fl_];
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(kr), qf[0], zc, 0, 0, 0);
-        dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(vr), dof[0], zc, 0, 0, 0);
-#pragma unroll
-        for (int t = 1; t < 4; ++t) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<const bf16x8*>(kr + t * 16), qf[t], s, 0, 0, 0);
-          dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<const bf16x8*>(vr + t * 16), dof[t], dp_, 0, 0, 0);
-        }
-      }
-      // softmax half at a time (8-float g liveness) + dq MFMAs
-      const bool diag = causal && (kv0 + 31 > qw + qoff);
-      bf16x8 gf0, gf1;
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        float g[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int r = half * 8 + j;
-          float p;
-          if (diag) {
-            int key = kv0 + drow(r, lane);
-            p = (key > myq + qoff)
-                    ? 0.f
-                    : __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
-          } else {
-            p = __builtin_amdgcn_exp2f(s[r] * s2scale - my_lse);
-          }
-          g[j] = scale * p * (dp_[r] - my_delta);
-        }
-        if (half == 0) gf0 = relayout8(g); else gf1 = relayout8(g);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const unsigned short* ak = &kt_lds[cur][(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        bf16x8 a0 = *reinterpret_cast<const bf16x8*>(ak);
-        bf16x8 a1 = *reinterpret_cast<const bf16x8*>(ak + 16);
-        dqa[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, gf0, dqa[mt], 0, 0, 0);
-        dqa[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, gf1, dqa[mt], 0, 0, 0);
-      }
-    }
-
-    if (have_next) {
-      // stage tile i+1 (loads issued after the MFMAs — registers are
-      // not live across compute; the 4th wave hides the latency)
-      s16x8 kst_n = stage_at(ksp + kstep);
-      s16x8 vst_n = stage_at(vsp + vstep);
-      stage_wr(kt_lds[cur ^ 1], kst_n);
-      *reinterpret_cast<s16x8*>(&krow_l[cur ^ 1][srow_ * KPAD + sd0_]) = kst_n;
-      *reinterpret_cast<s16x8*>(&vrow_l[cur ^ 1][srow_ * KPAD + sd0_]) = vst_n;
-      ksp += kstep;
-      vsp += vstep;
-    }
-    __syncthreads();  // buf[cur^1] writes visible; buf[cur] reads done
-    cur ^= 1;
-  }
-
-  if (myq < Tq) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int d = mt * 32 + drow(r, lane);
-        dqp[(long long)myq * dqsT + d] = f32_to_bf16(dqa[mt][r]);
-      }
+    for (int mt = 0; mt < 2; ++mt) drow_st(dqp + (long long)myq * dqs.T, mt, lane, dqa[mt]);
   }
 }
 
@@ -673,24 +582,30 @@ __global__ __launch_bounds__(256, 4) void attn_bwd_dq_np_kernel(
 //   S[q][key], P = exp2(s2 - lse2[q]); dP[q][key] = dO·V^T
 //   dV^T[d][key] += dO^T[d][q] · P[q][key]
 //   dK^T[d][key] += Q^T[d][q] · g[q][key]
+//
+// PIPE = true is the shipped form: the loop is software-pipelined across
+// q-tiles — the S/dP MFMAs of tile i+1 interleave with the dV/dK MFMAs of
+// tile i (all 6 accumulator chains independent), with tile i+2's staging
+// loads in flight.  That needs ~205 VGPRs — 2 waves/SIMD; instantiating
+// IT at 3 waves spills 39 regs (offline dump, profiles/kernel_resources.md).
+// PIPE = false is the non-pipelined form for the 3-waves/SIMD occupancy
+// point (QN_ATTN_DKV_OCC=3): the whole tile-i chain (S/dP -> softmax ->
+// dV/dK) runs inside one iteration so s/dp are TRANSIENT, the softmax
+// runs 8 values at a time, and the staging loads issue after the tile's
+// MFMAs, trading in-wave MFMA overlap for one extra resident wave to hide
+// the latency instead.  Same math, same LDS layout, ONE barrier per tile
+// in both forms.  Numerics gate for every instantiation:
+// tests/test_attention_variants_gpu.py.
 // ===========================================================================
-template <int MINW>
+template <int MINW, bool PIPE>
 __global__ __launch_bounds__(256, MINW) void attn_bwd_dkv_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
     const float* __restrict__ lse2, const float* __restrict__ delta,
     unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
-    int Tq, int Tk, int qoff, int H, float scale, int causal,
-    long long qsB, long long qsH, long long qsT,
-    long long ksB, long long ksH, long long ksT,
-    long long vsB, long long vsH, long long vsT,
-    long long dsB, long long dsH, long long dsT,
-    long long dksB, long long dksH, long long dksT,
-    long long dvsB, long long dvsH, long long dvsT) {
-  // double-buffered transpose tiles + per-tile lse/delta rows: the loop
-  // is software-pipelined across q-tiles — S/dP MFMAs of tile i+1
-  // interleave with the dV/dK MFMAs of tile i (all 6 accumulator chains
-  // independent), ONE barrier per tile.
+    int Tq, int Tk, int qoff, int H, float scale, int causal, AttnView qs,
+    AttnView ks, AttnView vs, AttnView dos, AttnView dks, AttnView dvs) {
+  // double-buffered transpose tiles + per-tile lse/delta rows
   __shared__ unsigned short dot_lds[2][64 * TPAD];
   __shared__ unsigned short qt_lds[2][64 * TPAD];
   // row-major q/dO tiles: shared fragment source for the S/dP MFMAs
@@ -708,18 +623,18 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dkv_kernel(
   const int kw = kv0b + wave * 32;
   const int mykey = kw + (lane & 31);
 
-  const unsigned short* qp = q + b * qsB + h * qsH;
-  const unsigned short* kp = k + b * ksB + h * ksH;
-  const unsigned short* vp = v + b * vsB + h * vsH;
-  const unsigned short* dop = dout + b * dsB + h * dsH;
-  unsigned short* dkp = dk + b * dksB + h * dksH;
-  unsigned short* dvp = dv + b * dvsB + h * dvsH;
+  const unsigned short* qp = q + b * qs.B + h * qs.H;
+  const unsigned short* kp = k + b * ks.B + h * ks.H;
+  const unsigned short* vp = v + b * vs.B + h * vs.H;
+  const unsigned short* dop = dout + b * dos.B + h * dos.H;
+  unsigned short* dkp = dk + b * dks.B + h * dks.H;
+  unsigned short* dvp = dv + b * dvs.B + h * dvs.H;
 
   bf16x8 kf[4], vf[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
-    kf[t] = frag_ld(kp, ksT, kw, t * 16, lane);
-    vf[t] = frag_ld(vp, vsT, kw, t * 16, lane);
+    kf[t] = frag_ld(kp, ks.T, kw, t * 16, lane);
+    vf[t] = frag_ld(vp, vs.T, kw, t * 16, lane);
   }
   const float s2scale = scale * LOG2E;
 
@@ -727,299 +642,106 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dkv_kernel(
 #pragma unroll
   for (int i = 0; i < 16; ++i) { dka[0][i] = dka[1][i] = dva[0][i] = dva[1][i] = 0.f; zc[i] = 0.f; }
 
-  // q loop is in LOCAL q space; keys at kv0b are causally visible to local
-  // q rows >= kv0b - qoff (qoff and kv0b are both multiples of 128)
+  // ---- causal window, key-major loop: block owns keys [kv0b, kv0b+128),
+  // wave keys [kw, kw+32), and walks 32-row q tiles at qt0 in LOCAL q
+  // space; keys at kv0b are causally visible to local q rows >= kv0b - qoff
+  // (qoff and kv0b are both multiples of 128)
   const int q_start = causal ? max(kv0b - qoff, 0) : 0;
   // pointer-bumped sources
-  const unsigned short* qfp = frag_base(qp, qsT, q_start, lane);
-  const unsigned short* dofp = frag_base(dop, dsT, q_start, lane);
-  const unsigned short* qsp = stage_base(qp, qsT, q_start);
-  const unsigned short* dosp = stage_base(dop, dsT, q_start);
+  const unsigned short* qsp = stage_base(qp, qs.T, q_start);
+  const unsigned short* dosp = stage_base(dop, dos.T, q_start);
   const float* lsep = lse2 + (long long)bh * Tq + q_start + threadIdx.x;
   const float* delp = delta + (long long)bh * Tq + q_start + threadIdx.x;
-  const long long qstep = 32 * qsT, dstep = 32 * dsT;
+  const long long qstep = 32 * qs.T, dstep = 32 * dos.T;
+  const int st_off = rowimg_st_off(), fr_off = rowimg_frag_off(lane);
 
   // ---- prologue: stage tile 0 into buf0 (transposed + row images) ---------
-  const int srow_ = threadIdx.x & 31;
-  const int sd0_ = (threadIdx.x >> 5) << 3;
   {
     s16x8 d0 = stage_at(dosp);
     s16x8 q0 = stage_at(qsp);
     stage_wr(dot_lds[0], d0);
     stage_wr(qt_lds[0], q0);
-    *reinterpret_cast<s16x8*>(&dorow[0][srow_ * KPAD + sd0_]) = d0;
-    *reinterpret_cast<s16x8*>(&qrow[0][srow_ * KPAD + sd0_]) = q0;
+    rowimg_st(dorow[0], st_off, d0);
+    rowimg_st(qrow[0], st_off, q0);
     if (threadIdx.x < 32) {
       lse_t[0][threadIdx.x] = *lsep;
       del_t[0][threadIdx.x] = *delp;
     }
   }
-  // prefetch tile 1's staging rows + lse/del
+  // PIPE: tile 1's staging rows + lse/del, prefetched across tile 0's compute
   s16x8 dost_n = {0, 0, 0, 0, 0, 0, 0, 0}, qst_n = dost_n;
   float lse_n = 0.f, del_n = 0.f;
-  if (q_start + 32 < Tq) {
-    dost_n = stage_at(dosp + dstep);
-    qst_n = stage_at(qsp + qstep);
-    if (threadIdx.x < 32) {
-      lse_n = lsep[32];
-      del_n = delp[32];
+  if constexpr (PIPE) {
+    if (q_start + 32 < Tq) {
+      dost_n = stage_at(dosp + dstep);
+      qst_n = stage_at(qsp + qstep);
+      if (threadIdx.x < 32) {
+        lse_n = lsep[32];
+        del_n = delp[32];
+      }
     }
   }
   __syncthreads();  // buf0 visible
-  // prime s/dp for tile 0 from the LDS row images (stride-72 reads are
-  // bank-conflict-free for the b128 fragment pattern)
-  const int fl_ = (lane & 31) * KPAD + ((lane >> 5) << 3);
   f32x16 s, dp_;
-  {
-    const unsigned short* qr = &qrow[0][fl_];
-    const unsigned short* dr = &dorow[0][fl_];
-    s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-        *reinterpret_cast<const bf16x8*>(qr), kf[0], zc, 0, 0, 0);
-    dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-        *reinterpret_cast<const bf16x8*>(dr), vf[0], zc, 0, 0, 0);
-#pragma unroll
-    for (int t = 1; t < 4; ++t) {
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(qr + t * 16), kf[t], s, 0, 0, 0);
-      dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(dr + t * 16), vf[t], dp_, 0, 0, 0);
-    }
-  }
+  // PIPE: prime s/dp for tile 0 from the LDS row images
+  if constexpr (PIPE) sdp_chain(&qrow[0][fr_off], &dorow[0][fr_off], kf, vf, zc, s, dp_);
 
   int cur = 0;
   for (int qt0 = q_start; qt0 < Tq; qt0 += 32) {
     const bool have_next = qt0 + 32 < Tq;
+    // the wave has at least one visible (q, key) pair in the tile
     const bool active = !(causal && qt0 + qoff + 31 < kw);
 
-    // softmax + relayout for tile i (s/dp computed last iteration).
-    // The 16 lse/delta rows a lane needs are 4 contiguous quadruples
-    // (drow: r&3 is the fast index) — 8 vector LDS loads issued together
-    // instead of 32 dependent ds_read_b32 round trips (the asm showed 24
-    // full lgkmcnt(0) drains per tile from the scalar form).
+    // softmax + relayout for tile i.  The 16 lse/delta rows a lane needs
+    // are 4 contiguous quadruples (drow: r&3 is the fast index) — 8 vector
+    // LDS loads issued together instead of 32 dependent ds_read_b32 round
+    // trips (the asm showed 24 full lgkmcnt(0) drains per tile from the
+    // scalar form).
     bf16x8 pf0, pf1, gf0, gf1;
     if (active) {
+      // !PIPE: S/dP for THIS tile from the row images (transient chains)
+      if constexpr (!PIPE)
+        sdp_chain(&qrow[cur][fr_off], &dorow[cur][fr_off], kf, vf, zc, s, dp_);
+      // the tile crosses the diagonal: only then is the per-element mask needed
       const bool diag = causal && (qt0 + qoff < kw + 31);
       const int lb = (lane >> 5) << 2;
-      float pv[16], gv[16];
-      if (diag) {
+      if constexpr (PIPE) {
+        float pv[16], gv[16];
+        if (diag) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          f32x4 lse4 = *reinterpret_cast<const f32x4*>(&lse_t[cur][lb + g * 8]);
-          f32x4 del4 = *reinterpret_cast<const f32x4*>(&del_t[cur][lb + g * 8]);
+          for (int g = 0; g < 4; ++g) {
+            f32x4 lse4 = *reinterpret_cast<const f32x4*>(&lse_t[cur][lb + g * 8]);
+            f32x4 del4 = *reinterpret_cast<const f32x4*>(&del_t[cur][lb + g * 8]);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            int r = g * 4 + j;
-            int qrow = drow(r, lane);
-            float p = (mykey > qt0 + qoff + qrow)
-                          ? 0.f
-                          : __builtin_amdgcn_exp2f(s[r] * s2scale - lse4[j]);
-            pv[r] = p;
-            gv[r] = scale * p * (dp_[r] - del4[j]);
+            for (int j = 0; j < 4; ++j) {
+              int r = g * 4 + j;
+              int qrow = drow(r, lane);
+              float p = (mykey > qt0 + qoff + qrow)
+                            ? 0.f
+                            : __builtin_amdgcn_exp2f(s[r] * s2scale - lse4[j]);
+              pv[r] = p;
+              gv[r] = scale * p * (dp_[r] - del4[j]);
+            }
+          }
+        } else {
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            f32x4 lse4 = *reinterpret_cast<const f32x4*>(&lse_t[cur][lb + g * 8]);
+            f32x4 del4 = *reinterpret_cast<const f32x4*>(&del_t[cur][lb + g * 8]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              int r = g * 4 + j;
+              float p = __builtin_amdgcn_exp2f(s[r] * s2scale - lse4[j]);
+              pv[r] = p;
+              gv[r] = scale * p * (dp_[r] - del4[j]);
+            }
           }
         }
+        pf0 = relayout8(pv); pf1 = relayout8(pv + 8);
+        gf0 = relayout8(gv); gf1 = relayout8(gv + 8);
       } else {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          f32x4 lse4 = *reinterpret_cast<const f32x4*>(&lse_t[cur][lb + g * 8]);
-          f32x4 del4 = *reinterpret_cast<const f32x4*>(&del_t[cur][lb + g * 8]);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            int r = g * 4 + j;
-            float p = __builtin_amdgcn_exp2f(s[r] * s2scale - lse4[j]);
-            pv[r] = p;
-            gv[r] = scale * p * (dp_[r] - del4[j]);
-          }
-        }
-      }
-      pf0 = relayout8(pv); pf1 = relayout8(pv + 8);
-      gf0 = relayout8(gv); gf1 = relayout8(gv + 8);
-    }
-
-    // stage tile i+1 into the other buffer (its last readers finished
-    // before the barrier of the previous iteration)
-    if (have_next) {
-      stage_wr(dot_lds[cur ^ 1], dost_n);
-      stage_wr(qt_lds[cur ^ 1], qst_n);
-      *reinterpret_cast<s16x8*>(&dorow[cur ^ 1][srow_ * KPAD + sd0_]) = dost_n;
-      *reinterpret_cast<s16x8*>(&qrow[cur ^ 1][srow_ * KPAD + sd0_]) = qst_n;
-      if (threadIdx.x < 32) {
-        lse_t[cur ^ 1][threadIdx.x] = lse_n;
-        del_t[cur ^ 1][threadIdx.x] = del_n;
-      }
-      // issue tile i+2 staging prefetch
-      qsp += qstep; dosp += dstep;
-      lsep += 32; delp += 32;
-      if (qt0 + 64 < Tq) {
-        dost_n = stage_at(dosp + dstep);
-        qst_n = stage_at(qsp + qstep);
-        if (threadIdx.x < 32) {
-          lse_n = lsep[32];
-          del_n = delp[32];
-        }
-      }
-    }
-
-    // dV/dK MFMAs for tile i (LDS buf[cur]) — interleaves with the
-    // S/dP MFMAs for tile i+1 below (independent accumulators)
-    if (active) {
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const unsigned short* adot = &dot_lds[cur][(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        const unsigned short* aqt = &qt_lds[cur][(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        bf16x8 d0 = *reinterpret_cast<const bf16x8*>(adot);
-        bf16x8 d1 = *reinterpret_cast<const bf16x8*>(adot + 16);
-        bf16x8 q0f = *reinterpret_cast<const bf16x8*>(aqt);
-        bf16x8 q1f = *reinterpret_cast<const bf16x8*>(aqt + 16);
-        dva[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d0, pf0, dva[mt], 0, 0, 0);
-        dva[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, pf1, dva[mt], 0, 0, 0);
-        dka[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(q0f, gf0, dka[mt], 0, 0, 0);
-        dka[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(q1f, gf1, dka[mt], 0, 0, 0);
-      }
-    }
-    __syncthreads();  // buf[cur^1] writes visible; buf[cur] reads done
-    if (have_next) {
-      // S/dP for tile i+1 from the freshly staged row images — the
-      // next iteration's writes target buf[cur], whose readers all
-      // finished before the barrier above
-      const unsigned short* qr = &qrow[cur ^ 1][fl_];
-      const unsigned short* dr = &dorow[cur ^ 1][fl_];
-      s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(qr), kf[0], zc, 0, 0, 0);
-      dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          *reinterpret_cast<const bf16x8*>(dr), vf[0], zc, 0, 0, 0);
-#pragma unroll
-      for (int t = 1; t < 4; ++t) {
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(qr + t * 16), kf[t], s, 0, 0, 0);
-        dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(dr + t * 16), vf[t], dp_, 0, 0, 0);
-      }
-    }
-    cur ^= 1;
-  }
-
-  if (mykey < Tk) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int d = mt * 32 + drow(r, lane);
-        dkp[(long long)mykey * dksT + d] = f32_to_bf16(dka[mt][r]);
-        dvp[(long long)mykey * dvsT + d] = f32_to_bf16(dva[mt][r]);
-      }
-  }
-}
-
-
-// Non-pipelined dkv variant for the 3-waves/SIMD occupancy point
-// (QN_ATTN_DKV_OCC=3).  The shipped kernel above software-pipelines
-// S/dP of tile i+1 against dV/dK of tile i, which needs ~205 VGPRs —
-// 2 waves/SIMD; instantiating IT at 3 waves spills 39 regs (offline
-// dump, profiles/kernel_resources.md).  Here the whole tile-i chain
-// (S/dP -> softmax -> dV/dK) runs inside one iteration so s/dp are
-// TRANSIENT, trading in-wave MFMA overlap for one extra resident wave
-// to hide the latency instead.  Same math, same LDS layout, single
-// barrier per tile.  Numerics gate: tests/test_ops_gpu.py attention
-// bwd oracles with QN_ATTN_DKV_OCC=3 (r3).
-__global__ __launch_bounds__(256, 3) void attn_bwd_dkv_np_kernel(
-    const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
-    const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
-    const float* __restrict__ lse2, const float* __restrict__ delta,
-    unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
-    int Tq, int Tk, int qoff, int H, float scale, int causal,
-    long long qsB, long long qsH, long long qsT,
-    long long ksB, long long ksH, long long ksT,
-    long long vsB, long long vsH, long long vsT,
-    long long dsB, long long dsH, long long dsT,
-    long long dksB, long long dksH, long long dksT,
-    long long dvsB, long long dvsH, long long dvsT) {
-  __shared__ unsigned short dot_lds[2][64 * TPAD];
-  __shared__ unsigned short qt_lds[2][64 * TPAD];
-  __shared__ unsigned short qrow[2][32 * KPAD];
-  __shared__ unsigned short dorow[2][32 * KPAD];
-  __shared__ alignas(16) float lse_t[2][32];
-  __shared__ alignas(16) float del_t[2][32];
-  const int bh = blockIdx.y;
-  const int b = bh / H, h = bh % H;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int kv0b = blockIdx.x * 128;
-  const int kw = kv0b + wave * 32;
-  const int mykey = kw + (lane & 31);
-
-  const unsigned short* qp = q + b * qsB + h * qsH;
-  const unsigned short* kp = k + b * ksB + h * ksH;
-  const unsigned short* vp = v + b * vsB + h * vsH;
-  const unsigned short* dop = dout + b * dsB + h * dsH;
-  unsigned short* dkp = dk + b * dksB + h * dksH;
-  unsigned short* dvp = dv + b * dvsB + h * dvsH;
-
-  bf16x8 kf[4], vf[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    kf[t] = frag_ld(kp, ksT, kw, t * 16, lane);
-    vf[t] = frag_ld(vp, vsT, kw, t * 16, lane);
-  }
-  const float s2scale = scale * LOG2E;
-
-  f32x16 dka[2], dva[2], zc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) { dka[0][i] = dka[1][i] = dva[0][i] = dva[1][i] = 0.f; zc[i] = 0.f; }
-
-  const int q_start = causal ? max(kv0b - qoff, 0) : 0;
-  const unsigned short* qsp = stage_base(qp, qsT, q_start);
-  const unsigned short* dosp = stage_base(dop, dsT, q_start);
-  const float* lsep = lse2 + (long long)bh * Tq + q_start + threadIdx.x;
-  const float* delp = delta + (long long)bh * Tq + q_start + threadIdx.x;
-  const long long qstep = 32 * qsT, dstep = 32 * dsT;
-
-  const int srow_ = threadIdx.x & 31;
-  const int sd0_ = (threadIdx.x >> 5) << 3;
-  {
-    s16x8 d0 = stage_at(dosp);
-    s16x8 q0 = stage_at(qsp);
-    stage_wr(dot_lds[0], d0);
-    stage_wr(qt_lds[0], q0);
-    *reinterpret_cast<s16x8*>(&dorow[0][srow_ * KPAD + sd0_]) = d0;
-    *reinterpret_cast<s16x8*>(&qrow[0][srow_ * KPAD + sd0_]) = q0;
-    if (threadIdx.x < 32) {
-      lse_t[0][threadIdx.x] = *lsep;
-      del_t[0][threadIdx.x] = *delp;
-    }
-  }
-  __syncthreads();
-
-  const int fl_ = (lane & 31) * KPAD + ((lane >> 5) << 3);
-  int cur = 0;
-  for (int qt0 = q_start; qt0 < Tq; qt0 += 32) {
-    const bool have_next = qt0 + 32 < Tq;
-    const bool active = !(causal && qt0 + qoff + 31 < kw);
-
-    if (active) {
-      // S/dP for THIS tile from the row images (transient chains)
-      f32x16 s, dp_;
-      {
-        const unsigned short* qr = &qrow[cur][fl_];
-        const unsigned short* dr = &dorow[cur][fl_];
-        s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(qr), kf[0], zc, 0, 0, 0);
-        dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-            *reinterpret_cast<const bf16x8*>(dr), vf[0], zc, 0, 0, 0);
-#pragma unroll
-        for (int t = 1; t < 4; ++t) {
-          s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<const bf16x8*>(qr + t * 16), kf[t], s, 0, 0, 0);
-          dp_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              *reinterpret_cast<const bf16x8*>(dr + t * 16), vf[t], dp_, 0, 0, 0);
-        }
-      }
-      // softmax + relayout, HALF at a time: pv/gv live 8 floats each
-      // instead of 16 (register pressure — this variant trades in-wave
-      // ILP for occupancy everywhere)
-      bf16x8 pf0, pf1, gf0, gf1;
-      {
-        const bool diag = causal && (qt0 + qoff < kw + 31);
-        const int lb = (lane >> 5) << 2;
+        // HALF at a time: pv/gv live 8 floats each instead of 16 (register
+        // pressure — this form trades in-wave ILP for occupancy everywhere)
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
           float pv[8], gv[8];
@@ -1048,154 +770,129 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_dkv_np_kernel(
           else           { pf1 = relayout8(pv); gf1 = relayout8(gv); }
         }
       }
-      // dV/dK from the transpose images
-#pragma unroll
-      for (int mt = 0; mt < 2; ++mt) {
-        const unsigned short* adot = &dot_lds[cur][(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        const unsigned short* aqt = &qt_lds[cur][(mt * 32 + (lane & 31)) * TPAD + ((lane >> 5) << 3)];
-        bf16x8 d0 = *reinterpret_cast<const bf16x8*>(adot);
-        bf16x8 d1 = *reinterpret_cast<const bf16x8*>(adot + 16);
-        bf16x8 q0f = *reinterpret_cast<const bf16x8*>(aqt);
-        bf16x8 q1f = *reinterpret_cast<const bf16x8*>(aqt + 16);
-        dva[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d0, pf0, dva[mt], 0, 0, 0);
-        dva[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(d1, pf1, dva[mt], 0, 0, 0);
-        dka[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(q0f, gf0, dka[mt], 0, 0, 0);
-        dka[mt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(q1f, gf1, dka[mt], 0, 0, 0);
+    }
+
+    // PIPE: stage tile i+1 into the other buffer (its last readers finished
+    // before the barrier of the previous iteration)
+    if constexpr (PIPE) {
+      if (have_next) {
+        stage_wr(dot_lds[cur ^ 1], dost_n);
+        stage_wr(qt_lds[cur ^ 1], qst_n);
+        rowimg_st(dorow[cur ^ 1], st_off, dost_n);
+        rowimg_st(qrow[cur ^ 1], st_off, qst_n);
+        if (threadIdx.x < 32) {
+          lse_t[cur ^ 1][threadIdx.x] = lse_n;
+          del_t[cur ^ 1][threadIdx.x] = del_n;
+        }
+        // issue tile i+2 staging prefetch
+        qsp += qstep; dosp += dstep;
+        lsep += 32; delp += 32;
+        if (qt0 + 64 < Tq) {
+          dost_n = stage_at(dosp + dstep);
+          qst_n = stage_at(qsp + qstep);
+          if (threadIdx.x < 32) {
+            lse_n = lsep[32];
+            del_n = delp[32];
+          }
+        }
       }
     }
 
-    if (have_next) {
-      // stage tile i+1 into the other buffer.  Loads are issued HERE,
-      // after the tile's MFMAs, so their registers are not live across
-      // the compute — at 3 waves/SIMD the other waves' compute covers
-      // the load latency that in-tile overlap covered at 2 waves.
-      s16x8 dost_n = stage_at(dosp + dstep);
-      s16x8 qst_n = stage_at(qsp + qstep);
-      stage_wr(dot_lds[cur ^ 1], dost_n);
-      stage_wr(qt_lds[cur ^ 1], qst_n);
-      *reinterpret_cast<s16x8*>(&dorow[cur ^ 1][srow_ * KPAD + sd0_]) = dost_n;
-      *reinterpret_cast<s16x8*>(&qrow[cur ^ 1][srow_ * KPAD + sd0_]) = qst_n;
-      if (threadIdx.x < 32) {
-        lse_t[cur ^ 1][threadIdx.x] = lsep[32];
-        del_t[cur ^ 1][threadIdx.x] = delp[32];
+    // dV/dK MFMAs for tile i (LDS buf[cur]) — under PIPE they interleave
+    // with the S/dP MFMAs for tile i+1 below (independent accumulators)
+    if (active) {
+#pragma unroll
+      for (int mt = 0; mt < 2; ++mt) {
+        tmfma2(dot_lds[cur], mt, lane, pf0, pf1, dva[mt]);
+        tmfma2(qt_lds[cur], mt, lane, gf0, gf1, dka[mt]);
       }
-      qsp += qstep; dosp += dstep;
-      lsep += 32; delp += 32;
+    }
+
+    if constexpr (!PIPE) {
+      if (have_next) {
+        // stage tile i+1 into the other buffer.  Loads are issued HERE,
+        // after the tile's MFMAs, so their registers are not live across
+        // the compute — at 3 waves/SIMD the other waves' compute covers
+        // the load latency that in-tile overlap covered at 2 waves.
+        dost_n = stage_at(dosp + dstep);
+        qst_n = stage_at(qsp + qstep);
+        stage_wr(dot_lds[cur ^ 1], dost_n);
+        stage_wr(qt_lds[cur ^ 1], qst_n);
+        rowimg_st(dorow[cur ^ 1], st_off, dost_n);
+        rowimg_st(qrow[cur ^ 1], st_off, qst_n);
+        if (threadIdx.x < 32) {
+          lse_t[cur ^ 1][threadIdx.x] = lsep[32];
+          del_t[cur ^ 1][threadIdx.x] = delp[32];
+        }
+        qsp += qstep; dosp += dstep;
+        lsep += 32; delp += 32;
+      }
     }
     __syncthreads();  // buf[cur^1] writes visible; buf[cur] reads done
+    if constexpr (PIPE) {
+      // S/dP for tile i+1 from the freshly staged row images — the next
+      // iteration's writes target buf[cur], whose readers all finished
+      // before the barrier above
+      if (have_next)
+        sdp_chain(&qrow[cur ^ 1][fr_off], &dorow[cur ^ 1][fr_off], kf, vf, zc, s, dp_);
+    }
     cur ^= 1;
   }
 
   if (mykey < Tk) {
 #pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int d = mt * 32 + drow(r, lane);
-        dkp[(long long)mykey * dksT + d] = f32_to_bf16(dka[mt][r]);
-        dvp[(long long)mykey * dvsT + d] = f32_to_bf16(dva[mt][r]);
-      }
+    for (int mt = 0; mt < 2; ++mt) {
+      drow_st(dkp + (long long)mykey * dks.T, mt, lane, dka[mt]);
+      drow_st(dvp + (long long)mykey * dvs.T, mt, lane, dva[mt]);
+    }
   }
 }
 
-// ---- launchers -------------------------------------------------------------
-struct AttnStrides {
-  long long qB, qH, qT, kB, kH, kT, vB, vH, vT, oB, oH, oT;
-};
-
-void attn_fwd_launch(const unsigned short* q, const unsigned short* k,
-                     const unsigned short* v, unsigned short* out, float* lse2,
-                     int B, int H, int Tq, int Tk, int qoff, float scale,
-                     int causal, const AttnStrides& st, hipStream_t stream) {
-  dim3 grid(Tq / 128, B * H);
-  static int occ = -1, klds = -1;
-  if (occ < 0) {
-    const char* e = getenv("QN_ATTN_FWD_OCC");
-    occ = e ? atoi(e) : 3;
-    const char* e2 = getenv("QN_ATTN_KLDS");
-    klds = (e2 && e2[0] == '0') ? 0 : 1;  // default ON: fwd 66.8->47.9 us (r2)
-  }
-#define QN_AFWD(MINW_, KL_)                                                    \
-  hipLaunchKernelGGL((attn_fwd_kernel<MINW_, KL_>), grid, dim3(256), 0,        \
-                     stream, q, k, v, out, lse2, Tq, Tk, qoff, H, scale,       \
-                     causal, st.qB, st.qH, st.qT, st.kB, st.kH, st.kT, st.vB,  \
-                     st.vH, st.vT, st.oB, st.oH, st.oT)
-  if (occ >= 4) {
-    if (klds) QN_AFWD(4, true); else QN_AFWD(4, false);
-  } else {
-    if (klds) QN_AFWD(3, true); else QN_AFWD(3, false);
-  }
-#undef QN_AFWD
+// ---- launchers (interface: attn.h) ----------------------------------------
+// Every knob is read once per process, on the first launch that needs it.
+static const char* knob(const char* name, const char* dflt) {
+  const char* e = std::getenv(name);
+  return e ? e : dflt;
 }
 
-void attn_delta_launch(const unsigned short* dout, const unsigned short* out,
-                       float* delta, int B, int H, int T,
-                       long long dsB, long long dsH, long long dsT,
-                       long long osB, long long osH, long long osT,
-                       hipStream_t stream) {
-  long long rows = (long long)B * H * T;
+void attn_fwd_launch(const AttnArgs& a, hipStream_t stream) {
+  static const int occ = atoi(knob("QN_ATTN_FWD_OCC", "3"));
+  // default ON: fwd 66.8->47.9 us (r2); only a leading '0' turns it off
+  static const bool klds = knob("QN_ATTN_KLDS", "1")[0] != '0';
+  auto kern = occ >= 4 ? (klds ? attn_fwd_kernel<4, true> : attn_fwd_kernel<4, false>)
+                       : (klds ? attn_fwd_kernel<3, true> : attn_fwd_kernel<3, false>);
+  hipLaunchKernelGGL(kern, dim3(a.Tq / 128, a.B * a.H), dim3(256), 0, stream,
+                     a.q.ptr, a.k.ptr, a.v.ptr, a.out.ptr, a.lse2, a.Tq, a.Tk,
+                     a.q_offset, a.H, a.scale, a.causal, a.q.st, a.k.st, a.v.st,
+                     a.out.st);
+}
+
+void attn_delta_launch(const AttnArgs& a, hipStream_t stream) {
+  long long rows = (long long)a.B * a.H * a.Tq;
   hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 15) / 16)),
-                     dim3(256), 0, stream, dout, out, delta, rows, T, H, dsB,
-                     dsH, dsT, osB, osH, osT);
+                     dim3(256), 0, stream, a.dout.ptr, a.out.ptr, a.delta, rows,
+                     a.Tq, a.H, a.dout.st, a.out.st);
 }
 
-void attn_bwd_dq_launch(const unsigned short* q, const unsigned short* k,
-                        const unsigned short* v, const unsigned short* dout,
-                        const float* lse2, const float* delta,
-                        unsigned short* dq, int B, int H, int Tq, int Tk,
-                        int qoff, float scale,
-                        int causal, const AttnStrides& st,
-                        long long dsB, long long dsH, long long dsT,
-                        hipStream_t stream) {
-  dim3 grid(Tq / 128, B * H);
-  static int occ = -1;
-  if (occ < 0) {
-    const char* e = getenv("QN_ATTN_DQ_OCC");
-    occ = e ? atoi(e) : 3;  // A/B r2: 3 waves/SIMD = bwd 279.8 -> 265.2 us
-  }
-  if (occ >= 4)  // non-pipelined 4-wave variant (see kernel comment)
-    hipLaunchKernelGGL(attn_bwd_dq_np_kernel, grid, dim3(256), 0, stream, q, k,
-                       v, dout, lse2, delta, dq, Tq, Tk, qoff, H, scale, causal,
-                       st.qB, st.qH, st.qT, st.kB, st.kH, st.kT, st.vB, st.vH,
-                       st.vT, dsB, dsH, dsT, st.oB, st.oH, st.oT);
-  else if (occ >= 3)
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<3>, grid, dim3(256), 0, stream, q, k,
-                       v, dout, lse2, delta, dq, Tq, Tk, qoff, H, scale, causal,
-                       st.qB, st.qH, st.qT, st.kB, st.kH, st.kT, st.vB, st.vH,
-                       st.vT, dsB, dsH, dsT, st.oB, st.oH, st.oT);
-  else
-    hipLaunchKernelGGL(attn_bwd_dq_kernel<2>, grid, dim3(256), 0, stream, q, k,
-                       v, dout, lse2, delta, dq, Tq, Tk, qoff, H, scale, causal,
-                       st.qB, st.qH, st.qT, st.kB, st.kH, st.kT, st.vB, st.vH,
-                       st.vT, dsB, dsH, dsT, st.oB, st.oH, st.oT);
+void attn_bwd_dq_launch(const AttnArgs& a, hipStream_t stream) {
+  // A/B r2: 3 waves/SIMD = bwd 279.8 -> 265.2 us; 4 = the non-pipelined form
+  static const int occ = atoi(knob("QN_ATTN_DQ_OCC", "3"));
+  auto kern = occ >= 4   ? attn_bwd_dq_kernel<4, false>
+              : occ >= 3 ? attn_bwd_dq_kernel<3, true>
+                         : attn_bwd_dq_kernel<2, true>;
+  hipLaunchKernelGGL(kern, dim3(a.Tq / 128, a.B * a.H), dim3(256), 0, stream,
+                     a.q.ptr, a.k.ptr, a.v.ptr, a.dout.ptr, a.lse2, a.delta,
+                     a.dq.ptr, a.Tq, a.Tk, a.q_offset, a.H, a.scale, a.causal,
+                     a.q.st, a.k.st, a.v.st, a.dout.st, a.dq.st);
 }
 
-void attn_bwd_dkv_launch(const unsigned short* q, const unsigned short* k,
-                         const unsigned short* v, const unsigned short* dout,
-                         const float* lse2, const float* delta,
-                         unsigned short* dk, unsigned short* dv, int B, int H,
-                         int Tq, int Tk, int qoff, float scale, int causal,
-                         const AttnStrides& st,
-                         long long dsB, long long dsH, long long dsT,
-                         long long dkB, long long dkH, long long dkT,
-                         long long dvB, long long dvH, long long dvT,
-                         hipStream_t stream) {
-  dim3 grid(Tk / 128, B * H);
-  // occupancy A/B (QN_ATTN_DKV_OCC): 2 = shipped/measured; 3 compiles
-  // clean per the offline resource dump (tools/dump_kernel_resources.py)
-  // and is the r3 candidate — semantics identical either way
-  static int occ = [] {
-    const char* e = std::getenv("QN_ATTN_DKV_OCC");
-    return e ? atoi(e) : 2;
-  }();
-  if (occ >= 3)
-    hipLaunchKernelGGL(attn_bwd_dkv_np_kernel, grid, dim3(256), 0, stream, q, k, v,
-                       dout, lse2, delta, dk, dv, Tq, Tk, qoff, H, scale, causal, st.qB,
-                       st.qH, st.qT, st.kB, st.kH, st.kT, st.vB, st.vH, st.vT,
-                       dsB, dsH, dsT, dkB, dkH, dkT, dvB, dvH, dvT);
-  else
-    hipLaunchKernelGGL(attn_bwd_dkv_kernel<2>, grid, dim3(256), 0, stream, q, k, v,
-                       dout, lse2, delta, dk, dv, Tq, Tk, qoff, H, scale, causal, st.qB,
-                       st.qH, st.qT, st.kB, st.kH, st.kT, st.vB, st.vH, st.vT,
-                       dsB, dsH, dsT, dkB, dkH, dkT, dvB, dvH, dvT);
+void attn_bwd_dkv_launch(const AttnArgs& a, hipStream_t stream) {
+  // 2 = shipped/measured (pipelined); 3 = the non-pipelined form, the r3
+  // occupancy candidate — semantics identical either way
+  static const int occ = atoi(knob("QN_ATTN_DKV_OCC", "2"));
+  auto kern = occ >= 3 ? attn_bwd_dkv_kernel<3, false> : attn_bwd_dkv_kernel<2, true>;
+  hipLaunchKernelGGL(kern, dim3(a.Tk / 128, a.B * a.H), dim3(256), 0, stream,
+                     a.q.ptr, a.k.ptr, a.v.ptr, a.dout.ptr, a.lse2, a.delta,
+                     a.dk.ptr, a.dv.ptr, a.Tq, a.Tk, a.q_offset, a.H, a.scale,
+                     a.causal, a.q.st, a.k.st, a.v.st, a.dout.st, a.dk.st, a.dv.st);
 }

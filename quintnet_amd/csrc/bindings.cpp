@@ -5,6 +5,8 @@
 
 #include <vector>
 
+#include "attn.h"
+
 // launcher decls (defined in the .hip TUs)
 template <typename T>
 void layernorm_fwd_launch(const T*, const T*, const T*, const T*, T*, T*, float*, float*, int, int, float, hipStream_t);
@@ -53,24 +55,6 @@ std::vector<at::Tensor> gemm_bias_gelu_aux(at::Tensor x, at::Tensor w,
 void gemm_nt_launch(const unsigned short*, const unsigned short*, const unsigned short*,
                     unsigned short*, unsigned short*, int, int, int, int, hipStream_t,
                     int mode = 0);
-struct AttnStrides {
-  long long qB, qH, qT, kB, kH, kT, vB, vH, vT, oB, oH, oT;
-};
-void attn_fwd_launch(const unsigned short*, const unsigned short*, const unsigned short*,
-                     unsigned short*, float*, int, int, int, int, int, float,
-                     int, const AttnStrides&, hipStream_t);
-void attn_delta_launch(const unsigned short*, const unsigned short*, float*, int, int, int,
-                       long long, long long, long long, long long, long long, long long,
-                       hipStream_t);
-void attn_bwd_dq_launch(const unsigned short*, const unsigned short*, const unsigned short*,
-                        const unsigned short*, const float*, const float*, unsigned short*,
-                        int, int, int, int, int, float, int, const AttnStrides&,
-                        long long, long long, long long, hipStream_t);
-void attn_bwd_dkv_launch(const unsigned short*, const unsigned short*, const unsigned short*,
-                         const unsigned short*, const float*, const float*, unsigned short*,
-                         unsigned short*, int, int, int, int, int, float, int, const AttnStrides&,
-                         long long, long long, long long, long long, long long, long long,
-                         long long, long long, long long, hipStream_t);
 struct DecodeStrides {
   long long qB, qH, qT, kB, kH, kT, vB, vH, vT, oB, oH, oT;
 };
@@ -523,6 +507,10 @@ const unsigned short* ap(const torch::Tensor& t) {
 unsigned short* ap_mut(torch::Tensor& t) {
   return reinterpret_cast<unsigned short*>(t.data_ptr<at::BFloat16>());
 }
+AttnTensor attn_tensor(const torch::Tensor& t) {
+  return {reinterpret_cast<unsigned short*>(t.data_ptr<at::BFloat16>()),
+          {t.stride(0), t.stride(1), t.stride(2)}};
+}
 }  // namespace
 
 torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -536,12 +524,13 @@ torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   check_attn_view(q, B, H, Tq); check_attn_view(k, B, H, Tk);
   check_attn_view(v, B, H, Tk); check_attn_view(out, B, H, Tq);
   auto lse2 = torch::empty({B * H, Tq}, q.options().dtype(torch::kFloat32));
-  AttnStrides st{q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-                 k.stride(2), v.stride(0), v.stride(1), v.stride(2), out.stride(0),
-                 out.stride(1), out.stride(2)};
-  attn_fwd_launch(ap(q), ap(k), ap(v), ap_mut(out), lse2.data_ptr<float>(),
-                  (int)B, (int)H, (int)Tq, (int)Tk, (int)q_offset, (float)scale,
-                  causal ? 1 : 0, st, cur_stream());
+  AttnArgs a{};
+  a.q = attn_tensor(q); a.k = attn_tensor(k); a.v = attn_tensor(v);
+  a.out = attn_tensor(out);
+  a.lse2 = lse2.data_ptr<float>();
+  a.B = (int)B; a.H = (int)H; a.Tq = (int)Tq; a.Tk = (int)Tk;
+  a.q_offset = (int)q_offset; a.scale = (float)scale; a.causal = causal ? 1 : 0;
+  attn_fwd_launch(a, cur_stream());
   return lse2;
 }
 
@@ -553,24 +542,16 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   check_attn_view(dout, B, H, Tq); check_attn_view(dq, B, H, Tq);
   check_attn_view(dk, B, H, Tk); check_attn_view(dv, B, H, Tk);
   auto delta = torch::empty({B * H, Tq}, q.options().dtype(torch::kFloat32));
-  attn_delta_launch(ap(dout), ap(out), delta.data_ptr<float>(), (int)B, (int)H,
-                    (int)Tq, dout.stride(0), dout.stride(1), dout.stride(2),
-                    out.stride(0), out.stride(1), out.stride(2), cur_stream());
-  AttnStrides st{q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1),
-                 k.stride(2), v.stride(0), v.stride(1), v.stride(2), dq.stride(0),
-                 dq.stride(1), dq.stride(2)};
-  attn_bwd_dq_launch(ap(q), ap(k), ap(v), ap(dout), lse2.data_ptr<float>(),
-                     delta.data_ptr<float>(), ap_mut(dq), (int)B, (int)H,
-                     (int)Tq, (int)Tk, (int)q_offset,
-                     (float)scale, causal ? 1 : 0, st, dout.stride(0),
-                     dout.stride(1), dout.stride(2), cur_stream());
-  attn_bwd_dkv_launch(ap(q), ap(k), ap(v), ap(dout), lse2.data_ptr<float>(),
-                      delta.data_ptr<float>(), ap_mut(dk), ap_mut(dv), (int)B,
-                      (int)H, (int)Tq, (int)Tk, (int)q_offset, (float)scale,
-                      causal ? 1 : 0, st,
-                      dout.stride(0), dout.stride(1), dout.stride(2),
-                      dk.stride(0), dk.stride(1), dk.stride(2), dv.stride(0),
-                      dv.stride(1), dv.stride(2), cur_stream());
+  AttnArgs a{};
+  a.q = attn_tensor(q); a.k = attn_tensor(k); a.v = attn_tensor(v);
+  a.out = attn_tensor(out); a.dout = attn_tensor(dout);
+  a.dq = attn_tensor(dq); a.dk = attn_tensor(dk); a.dv = attn_tensor(dv);
+  a.lse2 = lse2.data_ptr<float>(); a.delta = delta.data_ptr<float>();
+  a.B = (int)B; a.H = (int)H; a.Tq = (int)Tq; a.Tk = (int)Tk;
+  a.q_offset = (int)q_offset; a.scale = (float)scale; a.causal = causal ? 1 : 0;
+  attn_delta_launch(a, cur_stream());
+  attn_bwd_dq_launch(a, cur_stream());
+  attn_bwd_dkv_launch(a, cur_stream());
 }
 
 // fused decode attention over a static KV cache: append k_new/v_new at cache

@@ -42,8 +42,8 @@ def rows():
 def test_occupancy_variants_stay_spill_free(rows):
     budgets = {
         # kernel-name fragment: (max vgpr, min waves/SIMD) with 0 spills
-        "attn_bwd_dkv_np_kernel": (168, 3),
-        "attn_bwd_dq_np_kernel": (128, 4),
+        "attn_bwd_dkv_kernel<3, false>": (168, 3),
+        "attn_bwd_dq_kernel<4, false>": (128, 4),
         "wgrad_tn32_kernel": (128, 4),
     }
     for frag, (max_vgpr, min_waves) in budgets.items():
@@ -56,12 +56,12 @@ def test_occupancy_variants_stay_spill_free(rows):
 
 
 def test_default_kernels_stay_spill_free(rows):
-    for frag in ("attn_fwd_kernel<3, true>", "attn_bwd_dq_kernel<3>",
+    for frag in ("attn_fwd_kernel<3, true>", "attn_bwd_dq_kernel<3, true>",
                  "wgrad_tn_kernel"):
         match = [v for k, v in rows.items() if frag in k]
         assert match, frag
         assert match[0]["spill"] == 0, (frag, match[0])
     # the shipped dkv kernel: spill-free at its 2-wave point
     dkv = [v for k, v in rows.items()
-           if "attn_bwd_dkv_kernel<2>" in k]
+           if "attn_bwd_dkv_kernel<2, true>" in k]
     assert dkv and dkv[0]["spill"] == 0
