@@ -34,6 +34,9 @@
 //   attn_fwd_kernel<MINW, KLDS>      QN_ATTN_FWD_OCC (3 | 4), QN_ATTN_KLDS (1 | 0)
 //   attn_bwd_dq_kernel<MINW, PIPE>   QN_ATTN_DQ_OCC  (3 | 2 pipelined, 4 not)
 //   attn_bwd_dkv_kernel<MINW, PIPE>  QN_ATTN_DKV_OCC (2 pipelined, 3 not)
+// All three run a 1-D grid of T/128 * B*H blocks; attn_block_of (attn.h)
+// maps the block id to (row block, head), QN_ATTN_ORDER (balanced | linear)
+// picks the order for causal launches.
 // The passes share the leaf helpers below (row images, S/dP chain,
 // transposed-tile MFMAs, scatter store, q-major causal window) and take
 // their tensors as pointer + AttnView strides (attn.h).
@@ -42,6 +45,7 @@
 // Replaces reference F.scaled_dot_product_attention
 // (utils/GPT2/gpt2_attention.py:156).
 #include <cstdlib>
+#include <cstring>
 
 #include "attn.h"
 #include "common.h"
@@ -203,7 +207,8 @@ __device__ __forceinline__ bool qmajor_diag(bool causal, int kv0, int qw, int qo
 
 // ===========================================================================
 // forward
-// grid: (T/128, B*H); block 256.  Each wave owns 32 q rows.
+// grid: T/128 * B*H blocks, mapped to (q block, head) by attn_block_of
+// (attn.h); block 256.  Each wave owns 32 q rows.
 // q/k/v strided [.., T, 64] slices; out written via its own strides
 // (so [B, T, H*64] layout comes out directly); lse2 [BH, T] f32.
 // ===========================================================================
@@ -211,15 +216,16 @@ template <int MINW, bool KLDS>
 __global__ __launch_bounds__(256, MINW) void attn_fwd_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v, unsigned short* __restrict__ out,
-    float* __restrict__ lse2, int Tq, int Tk, int qoff, int H, float scale,
-    int causal, AttnView qs, AttnView ks, AttnView vs, AttnView os) {
+    float* __restrict__ lse2, int Tq, int Tk, int qoff, int H, int BH, int order,
+    float scale, int causal, AttnView qs, AttnView ks, AttnView vs, AttnView os) {
   __shared__ unsigned short vt[64 * TPAD + (KLDS ? 32 * KPAD : 0)];
   unsigned short* klds = vt + 64 * TPAD;  // [32][KPAD] row-major K tile
-  const int bh = blockIdx.y;
+  const AttnBlock wb = attn_block_of(blockIdx.x, Tq >> 7, BH, order);
+  const int bh = wb.bh;
   const int b = bh / H, h = bh % H;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int q0 = blockIdx.x * 128;        // block q range [q0, q0+128)
+  const int q0 = wb.blk * 128;            // block q range [q0, q0+128)
   const int qw = q0 + wave * 32;          // wave q range  [qw, qw+32)
   const int myq = qw + (lane & 31);       // this lane's q row
 
@@ -413,20 +419,21 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dq_kernel(
     const unsigned short* __restrict__ q, const unsigned short* __restrict__ k,
     const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
     const float* __restrict__ lse2, const float* __restrict__ delta,
-    unsigned short* __restrict__ dq, int Tq, int Tk, int qoff, int H,
-    float scale, int causal, AttnView qs, AttnView ks, AttnView vs, AttnView dos,
-    AttnView dqs) {
+    unsigned short* __restrict__ dq, int Tq, int Tk, int qoff, int H, int BH,
+    int order, float scale, int causal, AttnView qs, AttnView ks, AttnView vs,
+    AttnView dos, AttnView dqs) {
   // double-buffered K^T tile + row-major K/V images: the shared fragment
   // source for the S/dP MFMAs (replaces 4x-redundant per-wave global
   // fragment loads)
   __shared__ unsigned short kt_lds[2][64 * TPAD];
   __shared__ unsigned short krow_l[2][32 * KPAD];
   __shared__ unsigned short vrow_l[2][32 * KPAD];
-  const int bh = blockIdx.y;
+  const AttnBlock wb = attn_block_of(blockIdx.x, Tq >> 7, BH, order);
+  const int bh = wb.bh;
   const int b = bh / H, h = bh % H;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int q0 = blockIdx.x * 128;
+  const int q0 = wb.blk * 128;
   const int qw = q0 + wave * 32;
   const int myq = qw + (lane & 31);
 
@@ -603,8 +610,9 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dkv_kernel(
     const unsigned short* __restrict__ v, const unsigned short* __restrict__ dout,
     const float* __restrict__ lse2, const float* __restrict__ delta,
     unsigned short* __restrict__ dk, unsigned short* __restrict__ dv,
-    int Tq, int Tk, int qoff, int H, float scale, int causal, AttnView qs,
-    AttnView ks, AttnView vs, AttnView dos, AttnView dks, AttnView dvs) {
+    int Tq, int Tk, int qoff, int H, int BH, int order, float scale, int causal,
+    AttnView qs, AttnView ks, AttnView vs, AttnView dos, AttnView dks,
+    AttnView dvs) {
   // double-buffered transpose tiles + per-tile lse/delta rows
   __shared__ unsigned short dot_lds[2][64 * TPAD];
   __shared__ unsigned short qt_lds[2][64 * TPAD];
@@ -615,11 +623,12 @@ __global__ __launch_bounds__(256, MINW) void attn_bwd_dkv_kernel(
   __shared__ unsigned short dorow[2][32 * KPAD];
   __shared__ alignas(16) float lse_t[2][32];
   __shared__ alignas(16) float del_t[2][32];
-  const int bh = blockIdx.y;
+  const AttnBlock wb = attn_block_of(blockIdx.x, Tk >> 7, BH, order);
+  const int bh = wb.bh;
   const int b = bh / H, h = bh % H;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int kv0b = blockIdx.x * 128;
+  const int kv0b = wb.blk * 128;
   const int kw = kv0b + wave * 32;
   const int mykey = kw + (lane & 31);
 
@@ -855,16 +864,25 @@ static const char* knob(const char* name, const char* dflt) {
   return e ? e : dflt;
 }
 
+// QN_ATTN_ORDER: balanced (default) spreads the causal row blocks evenly
+// over the XCDs, heaviest first; linear is the dim3(T/128, B*H) order
+// (attn.h: attn_block_of).  Outputs are bit-identical either way.
+static int block_order(const AttnArgs& a, bool key_major) {
+  static const bool balanced = strcmp(knob("QN_ATTN_ORDER", "balanced"), "linear") != 0;
+  return attn_order_for(balanced, a.causal != 0, key_major);
+}
+
 void attn_fwd_launch(const AttnArgs& a, hipStream_t stream) {
   static const int occ = atoi(knob("QN_ATTN_FWD_OCC", "3"));
   // default ON: fwd 66.8->47.9 us (r2); only a leading '0' turns it off
   static const bool klds = knob("QN_ATTN_KLDS", "1")[0] != '0';
   auto kern = occ >= 4 ? (klds ? attn_fwd_kernel<4, true> : attn_fwd_kernel<4, false>)
                        : (klds ? attn_fwd_kernel<3, true> : attn_fwd_kernel<3, false>);
-  hipLaunchKernelGGL(kern, dim3(a.Tq / 128, a.B * a.H), dim3(256), 0, stream,
+  const int BH = a.B * a.H;
+  hipLaunchKernelGGL(kern, dim3(a.Tq / 128 * BH), dim3(256), 0, stream,
                      a.q.ptr, a.k.ptr, a.v.ptr, a.out.ptr, a.lse2, a.Tq, a.Tk,
-                     a.q_offset, a.H, a.scale, a.causal, a.q.st, a.k.st, a.v.st,
-                     a.out.st);
+                     a.q_offset, a.H, BH, block_order(a, false), a.scale,
+                     a.causal, a.q.st, a.k.st, a.v.st, a.out.st);
 }
 
 void attn_delta_launch(const AttnArgs& a, hipStream_t stream) {
@@ -880,10 +898,12 @@ void attn_bwd_dq_launch(const AttnArgs& a, hipStream_t stream) {
   auto kern = occ >= 4   ? attn_bwd_dq_kernel<4, false>
               : occ >= 3 ? attn_bwd_dq_kernel<3, true>
                          : attn_bwd_dq_kernel<2, true>;
-  hipLaunchKernelGGL(kern, dim3(a.Tq / 128, a.B * a.H), dim3(256), 0, stream,
+  const int BH = a.B * a.H;
+  hipLaunchKernelGGL(kern, dim3(a.Tq / 128 * BH), dim3(256), 0, stream,
                      a.q.ptr, a.k.ptr, a.v.ptr, a.dout.ptr, a.lse2, a.delta,
-                     a.dq.ptr, a.Tq, a.Tk, a.q_offset, a.H, a.scale, a.causal,
-                     a.q.st, a.k.st, a.v.st, a.dout.st, a.dq.st);
+                     a.dq.ptr, a.Tq, a.Tk, a.q_offset, a.H, BH,
+                     block_order(a, false), a.scale, a.causal, a.q.st, a.k.st,
+                     a.v.st, a.dout.st, a.dq.st);
 }
 
 void attn_bwd_dkv_launch(const AttnArgs& a, hipStream_t stream) {
@@ -891,8 +911,10 @@ void attn_bwd_dkv_launch(const AttnArgs& a, hipStream_t stream) {
   // occupancy candidate — semantics identical either way
   static const int occ = atoi(knob("QN_ATTN_DKV_OCC", "2"));
   auto kern = occ >= 3 ? attn_bwd_dkv_kernel<3, false> : attn_bwd_dkv_kernel<2, true>;
-  hipLaunchKernelGGL(kern, dim3(a.Tk / 128, a.B * a.H), dim3(256), 0, stream,
+  const int BH = a.B * a.H;
+  hipLaunchKernelGGL(kern, dim3(a.Tk / 128 * BH), dim3(256), 0, stream,
                      a.q.ptr, a.k.ptr, a.v.ptr, a.dout.ptr, a.lse2, a.delta,
-                     a.dk.ptr, a.dv.ptr, a.Tq, a.Tk, a.q_offset, a.H, a.scale,
-                     a.causal, a.q.st, a.k.st, a.v.st, a.dout.st, a.dk.st, a.dv.st);
+                     a.dk.ptr, a.dv.ptr, a.Tq, a.Tk, a.q_offset, a.H, BH,
+                     block_order(a, true), a.scale, a.causal, a.q.st, a.k.st,
+                     a.v.st, a.dout.st, a.dk.st, a.dv.st);
 }

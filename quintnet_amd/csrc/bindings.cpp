@@ -537,11 +537,25 @@ torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
               torch::Tensor out, torch::Tensor dout, torch::Tensor lse2,
               torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
-              double scale, bool causal, int64_t q_offset) {
+              double scale, bool causal, int64_t q_offset, int64_t parts,
+              c10::optional<torch::Tensor> delta_buf) {
+  // parts (for per-pass timing): 1 = delta + dq, 2 = dkv alone, which reads
+  // the delta_buf a parts = 1 call filled; 3 = the whole backward
   int64_t B = q.size(0), H = q.size(1), Tq = q.size(2), Tk = k.size(2);
   check_attn_view(dout, B, H, Tq); check_attn_view(dq, B, H, Tq);
   check_attn_view(dk, B, H, Tk); check_attn_view(dv, B, H, Tk);
-  auto delta = torch::empty({B * H, Tq}, q.options().dtype(torch::kFloat32));
+  TORCH_CHECK(parts >= 1 && parts <= 3, "attn_bwd: parts is 1, 2 or 3");
+  TORCH_CHECK((parts & 1) || delta_buf.has_value(),
+              "attn_bwd: dkv alone needs the delta of an earlier call");
+  if (delta_buf.has_value()) {
+    const torch::Tensor& d = *delta_buf;
+    TORCH_CHECK(d.is_cuda() && d.device() == q.device() && d.is_contiguous() &&
+                d.dtype() == torch::kFloat32 && d.numel() == B * H * Tq,
+                "attn_bwd: delta must be a contiguous f32 [B*H, Tq] on q's GPU");
+  }
+  auto delta = delta_buf.has_value()
+                   ? *delta_buf
+                   : torch::empty({B * H, Tq}, q.options().dtype(torch::kFloat32));
   AttnArgs a{};
   a.q = attn_tensor(q); a.k = attn_tensor(k); a.v = attn_tensor(v);
   a.out = attn_tensor(out); a.dout = attn_tensor(dout);
@@ -549,9 +563,11 @@ void attn_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   a.lse2 = lse2.data_ptr<float>(); a.delta = delta.data_ptr<float>();
   a.B = (int)B; a.H = (int)H; a.Tq = (int)Tq; a.Tk = (int)Tk;
   a.q_offset = (int)q_offset; a.scale = (float)scale; a.causal = causal ? 1 : 0;
-  attn_delta_launch(a, cur_stream());
-  attn_bwd_dq_launch(a, cur_stream());
-  attn_bwd_dkv_launch(a, cur_stream());
+  if (parts & 1) {
+    attn_delta_launch(a, cur_stream());
+    attn_bwd_dq_launch(a, cur_stream());
+  }
+  if (parts & 2) attn_bwd_dkv_launch(a, cur_stream());
 }
 
 // fused decode attention over a static KV cache: append k_new/v_new at cache
@@ -620,7 +636,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
         py::arg("dout"), py::arg("lse2"), py::arg("dq"), py::arg("dk"),
         py::arg("dv"), py::arg("scale"), py::arg("causal"),
-        py::arg("q_offset") = 0);
+        py::arg("q_offset") = 0, py::arg("parts") = 3,
+        py::arg("delta") = c10::nullopt);
+  // the kernels' block-to-work mapping, run on the host (attn.h)
+  m.def("attn_order_for", [](bool balanced, bool causal, bool key_major) {
+    return attn_order_for(balanced, causal, key_major);
+  }, "block order of a fwd/dq (key_major = false) or dkv launch",
+        py::arg("balanced"), py::arg("causal"), py::arg("key_major"));
+  m.def("attn_block_of", [](int64_t L, int64_t nblk, int64_t BH, int64_t order) {
+    TORCH_CHECK(nblk >= 1 && BH >= 1 && L >= 0 && L < nblk * BH,
+                "attn_block_of: L outside the grid");
+    AttnBlock w = attn_block_of((unsigned)L, (int)nblk, (int)BH, (int)order);
+    return std::make_pair(w.blk, w.bh);
+  }, "(row block, head) of linear block id L in a grid of nblk * BH blocks",
+        py::arg("L"), py::arg("nblk"), py::arg("BH"), py::arg("order"));
   m.def("attn_decode", &attn_decode,
         "fused decode attention over a static KV cache (D=64, 1..8 rows)",
         py::arg("q"), py::arg("k_new"), py::arg("v_new"), py::arg("kc"),

@@ -17,6 +17,7 @@ KNOBS = [
     ("QN_ATTN_KLDS", "1", "cooperative K-through-LDS staging"),
     ("QN_ATTN_DQ_OCC", "3", "4 = non-pipelined 4-wave dq variant"),
     ("QN_ATTN_DKV_OCC", "2", "3 = non-pipelined 3-wave dkv variant"),
+    ("QN_ATTN_ORDER", "balanced", "causal block order over the XCDs (balanced|linear)"),
     ("QN_GELU_EPI", "0", "hipBLASLt GELU_AUX_BIAS epilogue (exp.)"),
     ("QN_GRAPHS", "1", "whole-step hipGraph capture in bench"),
     ("QN_VOCAB_PAD", "128/0", "padded-vocab logits width (bench)"),
